@@ -17,6 +17,13 @@ N > 1   : STRONG scaling by default -- the ONE headline hierarchy is sharded ove
           (same-level ghost cells, coarse phi and coarse flame normal under the coarse-fine faces) into two grouped
           RCCL point-to-point exchanges on its own stream.  --scaling weak: N copies of the hierarchy side by side in x.
           `python bench.py --gpus N` without a launcher starts its own N ranks (torch.distributed.run).
+
+A plain run sets up, warms up, times the K steps (with the HIP events of the roofline object; roofline.traffic from the
+committed record) and prints the line.  --full adds what takes runs of its own: the live PMC traffic passes, the per-stage
+breakdown, the secondary workloads, the cpu_baseline leg and its parity_check.
+--dump-outputs DIR: after the timed steps, the 8 outputs of the last step (gx gy gz |g| Nx Ny Nz K, float64) at a fixed,
+seeded sample of at most 2^18 cells per level (global cell indices of the file's boxes, independent of the internal
+tiling) as DIR/level<l>_<field>.npy (rank<r>_ in front on a sharded run: the sampled cells that rank owns).
 """
 import argparse
 import json
@@ -810,6 +817,49 @@ def dry_run(args, rank, world):
         dist.destroy_process_group()
 
 
+OUT_FIELDS = ("gx", "gy", "gz", "gmag", "nx", "ny", "nz", "curv")  # out[8 s + 0..7] of slot s (include/peleanalysis_amd.h: pa_gradcurv_run)
+DUMP_BYTES = 48 << 20  # whole dump, every level and slot (limit 64 MB)
+
+
+def dump_outputs(path, torch, dev, Hfile, dls, touts, nslot, prefix=""):
+    """--dump-outputs: the output multifabs as the last step left them, at a fixed sample of cells per level.  The sample is
+    drawn from the FILE's boxes (Hfile, seed = level) and located in whatever tiling the levels are swept on, so two builds
+    with different internal tilings dump the same cells in the same order.  Every sampled cell this rank owns is written."""
+    from peleanalysis_amd.hierarchy import mf_layout
+    os.makedirs(path, exist_ok=True)
+    nmax = DUMP_BYTES // (8 * len(OUT_FIELDS) * nslot * len(dls))
+    for l, (lf, dl, tout) in enumerate(zip(Hfile.levels, dls, touts)):
+        fb = lf.boxes.astype(np.int64)
+        fn = (fb[:, 3:] - fb[:, :3] + 1)
+        ends = np.cumsum(fn.prod(axis=1))
+        if ends[-1] <= nmax:
+            g = np.arange(ends[-1], dtype=np.int64)
+        else:
+            g = np.unique(np.random.default_rng(l).integers(0, ends[-1], nmax, dtype=np.int64))
+        b = np.searchsorted(ends, g, side="right")
+        r = g - (ends[b] - fn[b].prod(axis=1))
+        ijk = fb[b, :3] + np.stack([r % fn[b, 0], (r // fn[b, 0]) % fn[b, 1], r // (fn[b, 0] * fn[b, 1])], axis=1)
+        # the swept boxes (this rank's, on a sharded run) that hold the sampled cells
+        sb = dl.level.boxes.astype(np.int64)
+        off, cs, _ = mf_layout(dl.level.boxes, 8 * nslot, 0)
+        flat = np.full(len(g), -1, dtype=np.int64)  # cell's offset in the buffer (component 0), -1: not on this rank
+        stride = np.zeros(len(g), dtype=np.int64)   # component stride of its box
+        for q in range(len(sb)):
+            lo, hi = sb[q, :3], sb[q, 3:]
+            inside = np.all((ijk >= lo) & (ijk <= hi), axis=1)
+            n = hi - lo + 1
+            d = ijk[inside] - lo
+            flat[inside] = off[q] + (d[:, 2] * n[1] + d[:, 1]) * n[0] + d[:, 0]
+            stride[inside] = cs[q]
+        mine = flat >= 0
+        flat, stride = flat[mine], stride[mine]
+        for s in range(nslot):
+            for c, name in enumerate(OUT_FIELDS):
+                idx = torch.from_numpy(flat + (8 * s + c) * stride).to(dev)
+                v = tout.index_select(0, idx).cpu().numpy().astype(np.float64)
+                np.save(os.path.join(path, f"{prefix}level{l}_" + (f"slot{s}_" if nslot > 1 else "") + name + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -826,9 +876,14 @@ def main():
     ap.add_argument("--per", type=str, default="1 1 0", help="periodicity flags x y z (headline: periodic x/y, wall z); single GPU only")
     ap.add_argument("--threshold", type=float, default=-1.0, help="diagnostic: threshold_prog / threshold_value of curvature.cpp:549-570 (< 0: off, the headline)")
     ap.add_argument("--traffic", choices=("live", "file", "none"), default="live",
-                    help="roofline.traffic: measured now by two rocprofv3 --pmc child passes (falls back to the committed figure), the committed figure, or null")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads (configs 2-4, grad only, small boxes)")
+                    help="roofline.traffic: measured now by two rocprofv3 --pmc child passes (--full only; falls back to the committed figure), the committed "
+                         "figure, or null")
+    ap.add_argument("--full", action="store_true", help="also the live PMC traffic passes, the per-stage breakdown, the secondary workloads and the "
+                                                         "cpu_baseline leg with its parity_check (a plain run: the headline line only)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR", help="write the last timed step's outputs at a fixed, seeded sample of cells "
+                                                                                 "as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary workloads (configs 2-4, grad only, small boxes)")
     ap.add_argument("--secondary-only", type=str, default="", help="diagnostic: skip the headline region and the CPU leg, run ONE secondary entry (e.g. irregular_amr)")
     ap.add_argument("--no-profile", action="store_true", help="diagnostic: no HIP events in the timed region (no roofline object)")
     ap.add_argument("--cpu-base", type=int, default=0, help="base size of the cpu_baseline sample (0: from the core count)")
@@ -1049,16 +1104,20 @@ def main():
     ctx.profile_enable(False)
     nk, ms_k = ctx.profile_read(1, reset=True)
     assert ctx.bc_errors() == 0
-    # per-stage breakdown from two further, untimed steps with every stage's launches timed
-    nbd = 2
-    ctx.profile_enable(True)
-    for _ in range(nbd):
-        step()
-    barrier()
-    ctx.profile_enable(False)
-    bd = {name: ctx.profile_read(tag)[1] / nbd for name, tag in (("gradcurv", 1), ("faces", 2), ("fill_boundary", 3), ("apply_bc", 4), ("progress", 6),
-                                                                  ("exchange", 9))}
-    ctx.profile_read(1, reset=True)  # a reset drops every tag's records
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, dev, Hfile, dls, hold[2::3], nslot, f"rank{rank}_" if world > 1 else "")
+    bd = None
+    if args.full:
+        # per-stage breakdown from two further, untimed steps with every stage's launches timed
+        nbd = 2
+        ctx.profile_enable(True)
+        for _ in range(nbd):
+            step()
+        barrier()
+        ctx.profile_enable(False)
+        bd = {name: ctx.profile_read(tag)[1] / nbd for name, tag in (("gradcurv", 1), ("faces", 2), ("fill_boundary", 3), ("apply_bc", 4), ("progress", 6),
+                                                                      ("exchange", 9))}
+        ctx.profile_read(1, reset=True)  # a reset drops every tag's records
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1112,7 +1171,7 @@ def main():
         traffic, kern = None, ctx.lib.pa_sweep_kernel_name(ctx.h).decode()
         traffic_src = None
         headline_cfg = (args.base, args.nlev, args.box, args.ncomp, world, args.sim_of) == (512, 3, 128, 1, 1, 0) and per == (1, 1, 0) and args.threshold < 0
-        if headline_cfg and args.traffic == "live" and rank == 0:
+        if headline_cfg and args.full and args.traffic == "live" and rank == 0:
             traffic, traffic_src = live_traffic(retile=args.retile)
         tj = os.path.join(ROOT, "profiles", "r06_headline_traffic.json" if args.retile else "r04_headline_traffic.json")
         if traffic is None and args.traffic != "none" and os.path.exists(tj) and headline_cfg:
@@ -1123,9 +1182,10 @@ def main():
         res["roofline"] = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
                            "traffic": traffic, "traffic_source": traffic_src, "kernel": kern + " (fused grad->curvature sweep)", "avg_launch_ms": avg_ms,
                            "launches": nk, "bytes_per_cell": BYTES_PER_CELL, "cells_per_launch": cells_local * args.ncomp * args.steps / nk}
-        res["breakdown_ms_per_step"] = bd  # from the untimed steps after the timed region (rank 0)
+        if bd is not None:
+            res["breakdown_ms_per_step"] = bd  # from the untimed steps after the timed region (rank 0)
         res["step_frac_of_hbm_roofline"] = (cells_local * args.ncomp * BYTES_PER_CELL / (dt / args.steps) / 1e9) / HBM_PEAK_GBS
-    if rank == 0 and world == 1 and not args.sim_of and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.sim_of and not args.no_secondary:
         try:
             del hold, states, works, outs  # the headline buffers (33 GB) make room for the secondary workloads
             torch.cuda.empty_cache()
@@ -1134,7 +1194,7 @@ def main():
             res["secondary"]["wall_s_incl_data_generation"] = round(time.perf_counter() - t0s, 2)
         except Exception as e:  # the headline line must survive a failure here
             res["secondary"] = {"error": repr(e)[:300]}
-    if rank == 0 and world == 1 and not args.no_cpu and not args.sim_of:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not args.sim_of:
         try:
             # bounded sample (~10-30 s of CPU work): a 3-level hierarchy sized from the host core count
             cores = usable_cpus()
