@@ -429,6 +429,44 @@ int pa_stream_trace(pa_ctx*, int nlev, pa_mf* const* vfield, int vcomp, int64_t 
 int pa_stream_trace_ranks(pa_ctx*, int nlev, pa_mf* const* vfield, int vcomp, int64_t nseed, const double* seeds, int nsteps,
                           double dt, double* dev_pos, int32_t* nredist /* may be NULL */, int share_flags);
 
+/* ------------------------------------------------------------- gradient streamlines (stream.cpp / stream_nd.f90)
+ * Lines of the progress variable's gradient (or of the velocity, traceAlongV) seeded on isosurface nodes, one
+ * (level, file box) per seed; each line only reads its own box's FAB.  The arithmetic is stream_nd.f90's:
+ * ntrpv (closed [plo, phi] test, trilinear sum in the Fortran's term order), vnrml (normalise only if
+ * |v|^2 > (double)1.e-12f, divide by the square root), RK4 ending x + (k1+k4)/6 + (k2+k3)/3.
+ *
+ * One MFIter iteration of stream.cpp:920-925, vtrace(...) with device pointers: T holds nT components
+ * (progress first) on T->lo..T->hi; loc: nloc node coordinates, component-major (loc[c * nloc + j]); ids:
+ * n_ids 1-based node ids (device); g: 3 components, WRITTEN with g = T(i+1) - T(i-1) per direction over
+ * g->lo..g->hi when computeVec = 1, read as the vector field when 0 (g may then alias components of T);
+ * strm: ncs = 3 + nT components on (0, -nRKh, 0)..(n_ids-1, nRKsteps-1-nRKh, 0) = strm->lo..strm->hi;
+ * dx / plo / phi / hRK: host values as vtrace gets them.  *errFlag: vtrace's final errFlag (0, 1 "Problem
+ * with interpolation", 2 / 4 a backward / forward line was cut short -- the LAST such event of the box, as
+ * the Fortran assigns it).  Synchronous. */
+int pa_vtrace_fab(pa_ctx*, const pa_fab* T, int32_t nT, const double* loc, int64_t nloc, const int32_t* ids, int32_t n_ids,
+                  pa_fab* g, int32_t computeVec, pa_fab* strm, int32_t ncs, const double dx[3], const double plo[3],
+                  const double phi[3], double hRK, int32_t* errFlag);
+/* State of stream.cpp:796-884 for the whole hierarchy, in place, levels coarse to fine: state[l] holds the
+ * plotfile's data in the valid cells (components 0..ncomp-1, nGrow = state[l]'s ghost width) and gets every
+ * ghost cell set as FillBoundary -> FillCFgrowCells (piecewise-constant copy of the PREPARED coarse level,
+ * its ghost cells included) -> FillBoundary -> FixOOB leave it: cells outside the index domain 0 (periodic
+ * images too: is_per has no effect), cells of another box of the level its valid value, other cells the
+ * coarse value of their parent (0 on level 0).  The refinement ratio of each level pair is taken from the
+ * domains.  Returns non-zero where the reference would read a coarse value it never set (a parent cell that
+ * no coarse FAB holds, or that a fine box partly covers).  Asynchronous on the context's stream. */
+int pa_streamgrad_prepare(pa_ctx*, int nlev, pa_mf* const* state);
+/* vtrace of every (level, box) that holds seeds, in ONE launch, two threads per seed (backward, forward).
+ * state: pa_streamgrad_prepare's result, nT = its component count, vcomp: first velocity component
+ * (traceAlongV) or -1 (the gradient of component 0, formed on the fly = the reference's g); nodes: device,
+ * component-major [3][nnodes]; boxes of all levels numbered globally (level 0's first, file order);
+ * box_start: host CSR [nbox_total + 1] of the lines per box; ids: device, 1-based node id per line in that
+ * order; strm: device, the Str FABs of the boxes with lines back to back (box g at box_start[g] * nRKsteps *
+ * (3 + nT) doubles, i fastest, then n + nRKh, component outermost).  box_flag: host [nbox_total], vtrace's
+ * final errFlag per box (0 for boxes without lines).  Synchronous. */
+int pa_streamgrad_trace(pa_ctx*, int nlev, pa_mf* const* state, int vcomp, int64_t nnodes, const double* nodes,
+                        const int64_t* box_start, const int32_t* ids, int nRKsteps, double hRK, double* strm,
+                        int32_t* box_flag);
+
 /* ------------------------------------------------------------ tool pipelines
  * The level loops of the tool mains, operating on device-resident MultiFabs.
  * levels/state/out are arrays of nlev pointers, coarse first. */

@@ -176,6 +176,10 @@ def load_library() -> C.CDLL:
         "pa_last_slow_cells": (C.c_int, [vp]),
         "pa_level_irregular_cells": (i64, [vp, vp]),
         "pa_stream_trace_ranks": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.c_int, i64, pdbl, C.c_int, dbl, vp, pi32, C.c_int]),
+        "pa_vtrace_fab": (C.c_int, [vp, C.POINTER(PaFab), i32, vp, i64, vp, i32, C.POINTER(PaFab), i32, C.POINTER(PaFab), i32, pdbl, pdbl, pdbl, dbl,
+                                    pi32]),
+        "pa_streamgrad_prepare": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+        "pa_streamgrad_trace": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.c_int, i64, vp, C.POINTER(i64), vp, C.c_int, dbl, vp, pi32]),
         "pa_smooth_last": (C.c_int, [vp, C.POINTER(C.c_int), pdbl]),
         "pa_curvature_last_path": (C.c_int, [vp]),
         "pa_level_free_scratch": (i64, [vp]),
@@ -591,6 +595,92 @@ def stream_trace(ctx, vfield, vcomp, seeds, nsteps, dt):
     ctx.check(ctx.lib.pa_stream_trace(ctx.h, len(vfield), _handles(vfield), int(vcomp), n, seeds.ctypes.data_as(C.POINTER(C.c_double)), int(nsteps),
                                       float(dt), C.c_void_p(buf.ptr), C.byref(nred)))
     return buf.to_numpy(np.float64, (2 * n, nsteps, 3)), nred.value
+
+
+def _dev_fab(buf: "DevBuf", lo, shape_zyx, ncomp: int, comp0: int = 0) -> PaFab:
+    """PaFab over a dense FAB [ncomp][nz][ny][nx] in buf whose cell lo..lo+shape-1 (component comp0 first)"""
+    f = PaFab()
+    n = int(np.prod(shape_zyx))
+    f.p = buf.ptr + 8 * comp0 * n
+    for d in range(3):
+        f.lo[d] = int(lo[d])
+        f.hi[d] = int(lo[d]) + int(shape_zyx[2 - d]) - 1
+    f.ncomp = int(ncomp) - int(comp0)
+    f.nstride = n
+    return f
+
+
+def vtrace_fab(ctx: Context, T: np.ndarray, T_lo, loc: np.ndarray, ids, nRKsteps: int, dx, plo, phi, hRK: float, g_lo=None, g_hi=None, vcomp=None):
+    """pa_vtrace_fab: vtrace of stream_nd.f90 on one FAB.  T [nT][nz][ny][nx] on T_lo..; loc [3][N] node coordinates; ids 1-based.
+    vcomp None: computeVec = 1 with g over g_lo..g_hi (default: T's box grown by -1); else the vector field is T's components
+    vcomp..vcomp+2 over T's box (traceAlongV).  -> (strm [3+nT][nRKsteps][n_ids], g [3][..] or None, errFlag)"""
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    loc = np.ascontiguousarray(loc, dtype=np.float64)
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    nT, n = T.shape[0], len(ids)
+    nRKh = (nRKsteps - 1) // 2
+    tb = DevBuf.from_numpy(ctx, T)
+    tf = _dev_fab(tb, T_lo, T.shape[1:], nT)
+    if vcomp is None:
+        glo = np.asarray(T_lo if g_lo is None else g_lo) + (1 if g_lo is None else 0)
+        ghi = (np.asarray(T_lo) + np.array(T.shape[:0:-1]) - 2) if g_hi is None else np.asarray(g_hi)
+        gshape = tuple(int(v) for v in (ghi - glo + 1)[::-1])
+        gb = DevBuf(ctx, 8 * 3 * int(np.prod(gshape)))
+        gf = _dev_fab(gb, glo, gshape, 3)
+    else:
+        gb, gshape = None, None
+        gf = _dev_fab(tb, T_lo, T.shape[1:], nT, vcomp)
+    lb = DevBuf.from_numpy(ctx, loc)
+    ib = DevBuf.from_numpy(ctx, ids if n else np.zeros(1, np.int32))
+    sb = DevBuf(ctx, max(8, 8 * (3 + nT) * nRKsteps * n))
+    sf = _dev_fab(sb, (0, -nRKh, 0), (1, nRKsteps, max(n, 1)), 3 + nT)
+    sf.hi[0] = n - 1
+    err = C.c_int32(0)
+    ctx.check(ctx.lib.pa_vtrace_fab(ctx.h, C.byref(tf), nT, C.c_void_p(lb.ptr), loc.shape[1], C.c_void_p(ib.ptr), n, C.byref(gf), 1 if vcomp is None else 0,
+                                    C.byref(sf), 3 + nT, _d3(dx), _d3(plo), _d3(phi), float(hRK), C.byref(err)))
+    strm = sb.to_numpy(np.float64, (3 + nT, nRKsteps, n))
+    g = gb.to_numpy(np.float64, (3,) + gshape) if gb is not None else None
+    return strm, g, err.value
+
+
+def streamgrad_prepare(ctx: Context, states: Sequence[DevMF]):
+    """pa_streamgrad_prepare: the ghost cells of stream.cpp:796-884 on every level, in place"""
+    ctx.check(ctx.lib.pa_streamgrad_prepare(ctx.h, len(states), _handles(states)))
+
+
+def streamgrad_trace(ctx: Context, states: Sequence[DevMF], nodes: np.ndarray, ins, nRKsteps: int, hRK: float, vcomp=None):
+    """pa_streamgrad_trace.  nodes [3][N]; ins[l][b] = 1-based node ids of (level l, box b).  -> (per level per box: strm
+    [3+nT][nRKsteps][n] or None, per level per box errFlag)"""
+    nodes = np.ascontiguousarray(nodes, dtype=np.float64)
+    counts = [len(ids) for per in ins for ids in per]
+    start = np.zeros(len(counts) + 1, dtype=np.int64)
+    start[1:] = np.cumsum(counts)
+    nlines = int(start[-1])
+    ncs = 3 + states[0].ncomp
+    allids = np.concatenate([np.asarray(ids, np.int32) for per in ins for ids in per] + [np.zeros(0, np.int32)])
+    nb = DevBuf.from_numpy(ctx, nodes)
+    ib = DevBuf.from_numpy(ctx, allids if nlines else np.zeros(1, np.int32))
+    sb = DevBuf(ctx, max(8, 8 * nlines * nRKsteps * ncs))
+    flags = np.zeros(len(counts), dtype=np.int32)
+    ctx.check(ctx.lib.pa_streamgrad_trace(ctx.h, len(states), _handles(states), -1 if vcomp is None else int(vcomp), nodes.shape[1], C.c_void_p(nb.ptr),
+                                          start.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(ib.ptr), int(nRKsteps), float(hRK), C.c_void_p(sb.ptr),
+                                          flags.ctypes.data_as(C.POINTER(C.c_int32))))
+    flat = sb.to_numpy(np.float64, (max(nlines, 1) * nRKsteps * ncs,))
+    out, fl, g = [], [], 0
+    for per in ins:
+        o, f = [], []
+        for ids in per:
+            n = len(ids)
+            if n == 0:
+                o.append(None)
+            else:
+                s0 = int(start[g]) * nRKsteps * ncs
+                o.append(flat[s0:s0 + n * nRKsteps * ncs].reshape(ncs, nRKsteps, n).copy())
+            f.append(int(flags[g]))
+            g += 1
+        out.append(o)
+        fl.append(f)
+    return out, fl
 
 
 def iso_merge(ctx: Context, fragments, ncomp: int):

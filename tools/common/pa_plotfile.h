@@ -107,6 +107,7 @@ struct PlotfileHeader {
   double prob_lo[3], prob_hi[3];
   std::vector<int> ref_ratio;
   std::vector<LevelMeta> lev;
+  std::vector<std::array<double, 3>> file_dx;  // AmrData::DxLevel: the dx lines of the Header
   std::string path;
   int comp(const std::string& n) const {
     for (size_t i = 0; i < names.size(); ++i)
@@ -228,7 +229,13 @@ inline PlotfileHeader read_header(const std::string& path, int dim_wanted = 3, b
   }
   for (int l = 0; l < H.nlev; ++l) f >> H.lev[l].level_step;
   std::getline(f, line);
-  for (int l = 0; l < H.nlev; ++l) std::getline(f, line);  // dx (recomputed like amrex::Geometry)
+  H.file_dx.resize(H.nlev);
+  for (int l = 0; l < H.nlev; ++l) {  // dx as written (the tools recompute it like amrex::Geometry; stream3d's push_nodes_inside uses it)
+    std::getline(f, line);
+    std::stringstream ss(line);
+    for (int d = 0; d < 3; ++d) H.file_dx[l][d] = 0.0;
+    for (int d = 0; d < dim; ++d) ss >> H.file_dx[l][d];
+  }
   std::getline(f, line);                                   // coord sys
   std::getline(f, line);                                   // boundary width
   for (int l = 0; l < H.nlev; ++l) {
@@ -336,6 +343,23 @@ inline std::string g17(double v) {
   char s[64];
   std::snprintf(s, sizeof s, "%.17g", v);
   return s;
+}
+
+// VisMF header of a ghost-free multifab whose FABs lie in ONE data file `dname` at offsets offs (Cell_H of a plotfile level;
+// Str_H of stream3d's streamFile): box strings, per-FAB minima / maxima of every component
+inline void write_vismf_header(const std::string& file, const std::string& dname, int ncomp, const std::vector<std::string>& boxes,
+                               const std::vector<long long>& offs, const std::vector<std::vector<double>>& mins, const std::vector<std::vector<double>>& maxs) {
+  const size_t nb = boxes.size();
+  std::ofstream h(file);
+  if (!h) Abort("Unable to create " + file);
+  h << "1\n1\n" << ncomp << "\n0\n(" << nb << " 0\n";
+  for (auto& B : boxes) h << B << "\n";
+  h << ")\n" << nb << "\n";
+  for (size_t b = 0; b < nb; ++b) h << "FabOnDisk: " << dname << " " << offs[b] << "\n";
+  h << "\n" << nb << "," << ncomp << "\n";
+  for (auto& m : mins) { for (double v : m) h << g17(v) << ","; h << "\n"; }
+  h << "\n" << nb << "," << ncomp << "\n";
+  for (auto& m : maxs) { for (double v : m) h << g17(v) << ","; h << "\n"; }
 }
 
 // WriteMultiLevelPlotfile restated: valid cells of comps [0, names.size()) of each level's HostMF
@@ -488,15 +512,9 @@ inline void write_plotfile(const std::string& path, const std::vector<std::strin
       ::close(fd);
       for (int x : bad) if (x) Abort("short write to " + fname + (file_boxes ? " (or the output BoxArray does not match the computed tiling)" : ""));
     }
-    std::ofstream h(dir + "/Cell_H");
-    h << "1\n1\n" << ncomp << "\n0\n(" << nb << " 0\n";
-    for (auto& B : WB) h << bstr(B) << "\n";
-    h << ")\n" << nb << "\n";
-    for (size_t b = 0; b < nb; ++b) h << "FabOnDisk: Cell_D_00000 " << offs[b] << "\n";
-    h << "\n" << nb << "," << ncomp << "\n";
-    for (auto& m : mins) { for (double v : m) h << g17(v) << ","; h << "\n"; }
-    h << "\n" << nb << "," << ncomp << "\n";
-    for (auto& m : maxs) { for (double v : m) h << g17(v) << ","; h << "\n"; }
+    std::vector<std::string> bs;
+    for (auto& B : WB) bs.push_back(bstr(B));
+    write_vismf_header(dir + "/Cell_H", "Cell_D_00000", ncomp, bs, offs, mins, maxs);
   }
 }
 
