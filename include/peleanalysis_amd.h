@@ -467,6 +467,39 @@ int pa_streamgrad_trace(pa_ctx*, int nlev, pa_mf* const* state, int vcomp, int64
                         const int64_t* box_start, const int32_t* ids, int nRKsteps, double hRK, double* strm,
                         int32_t* box_flag);
 
+/* ------------------------------------------------------------- sampling along streamlines (sampleStreamlines.cpp / _nd.f90)
+ * The arithmetic is sampleStreamlines_nd.f90's: ntrpv WITHOUT the [plo, phi] test (b = FLOOR((x-plo)/dx - 0.5), n clamped
+ * to [0, 1], the trilinear sum in the Fortran's term order); a point fails when b is outside [lo, hi - 1] of the data
+ * (the Fortran's b > hi test reads b + 1 outside the FAB at b == hi: a failure here).
+ *
+ * One MFIter iteration of sampleStreamlines.cpp:745-748, interpstream(...) with device pointers: loc = the path FAB (nl >= 3
+ * components, X / Y / Z first; its box holds j = 0, the seeds), fab = the staged data (np components), strm = np components
+ * on loc's box (the caller points it at component dComp of the sample FAB).  *status: 0, 1 "Seed not in valid region for
+ * interp", 2 "Interp bad, increase nGrow" -- the FIRST failing point in the Fortran's loop order decides (k, then j = 0 down
+ * to lo, then j = 1 .. hi, i innermost); failing points write nothing.  Synchronous. */
+int pa_interpstream_fab(pa_ctx*, const pa_fab* loc, int32_t nl, const pa_fab* fab, int32_t np, pa_fab* strm, const double dx[3],
+                        const double plo[3], int32_t* status);
+/* set_distance (sampleStreamlines.cpp:772): res(i, j, k) = the arc length from the seed along line i, negative for j < 0;
+ * res(i, 0, 0) = 0 (k = 0 hard-coded as in the Fortran: the box must hold j = 0 and k = 0).  res on loc's box.  Synchronous. */
+int pa_set_distance_fab(pa_ctx*, const pa_fab* loc, pa_fab* res);
+/* sample_pathlines + set_sample_location + set_sample_distance (sampleStreamlines.cpp:176-194) for the whole hierarchy, without
+ * the staged FABs: data[l] = components 0..K-1 of the plotfile on level l (any ghost width; only FABs that some grown seed box
+ * can reach need to hold data); file_dx: host [nlev][3], the plotfile header's dx; nbox: host [nlev] Str boxes per level;
+ * str_boxes: host [nbt][6] (lo, hi), each (ilo, jlo, 0)..(ihi, jhi, 0) with jlo <= 0 <= jhi; has_lines: host [nbt], non-zero
+ * for the boxes with inside_nodes (only those are sampled); bbox: host [nbt][6], the grown seed box of find_containing_box
+ * (:503-536, :620-621); xyz: device, X / Y / Z of box g at 3 * o_g doubles (component-major, i fastest, then j), o_g = the
+ * points of the boxes before g; out: device, ncout components of box g at ncout * o_g.  Writes components dcomp .. dcomp+K-1
+ * (0 in boxes without lines) and, with with_xyzd != 0, components 0..2 = X / Y / Z and 3 = distance_from_seed of every box.
+ * A corner cell of level lev inside the domain takes the value of the finest level <= lev that holds it (FillVar,
+ * piecewise-constant); outside, its periodic image's (one domain length at most, is_per directions) or -20000.
+ * box_fail: host [nbt], 0 or the status of pa_interpstream_fab for that box.  Synchronous. */
+int pa_streamsample_run(pa_ctx*, int nlev, pa_mf* const* data, int32_t K, const double* file_dx, const double plo[3],
+                        const int32_t is_per[3], const int32_t* nbox, const int32_t* str_boxes, const int32_t* has_lines,
+                        const int32_t* bbox, const double* xyz, double* out, int32_t ncout, int32_t dcomp, int32_t with_xyzd,
+                        int32_t* box_fail);
+/* hipMemGetInfo of the context's device: the tools size their passes by it */
+int pa_device_mem_info(pa_ctx*, int64_t* free_bytes, int64_t* total_bytes);
+
 /* ------------------------------------------------------------ tool pipelines
  * The level loops of the tool mains, operating on device-resident MultiFabs.
  * levels/state/out are arrays of nlev pointers, coarse first. */

@@ -180,6 +180,10 @@ def load_library() -> C.CDLL:
                                     pi32]),
         "pa_streamgrad_prepare": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
         "pa_streamgrad_trace": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.c_int, i64, vp, C.POINTER(i64), vp, C.c_int, dbl, vp, pi32]),
+        "pa_interpstream_fab": (C.c_int, [vp, C.POINTER(PaFab), i32, C.POINTER(PaFab), i32, C.POINTER(PaFab), pdbl, pdbl, pi32]),
+        "pa_set_distance_fab": (C.c_int, [vp, C.POINTER(PaFab), C.POINTER(PaFab)]),
+        "pa_streamsample_run": (C.c_int, [vp, C.c_int, C.POINTER(vp), i32, pdbl, pdbl, pi32, pi32, pi32, pi32, pi32, vp, vp, i32, i32, i32, pi32]),
+        "pa_device_mem_info": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
         "pa_smooth_last": (C.c_int, [vp, C.POINTER(C.c_int), pdbl]),
         "pa_curvature_last_path": (C.c_int, [vp]),
         "pa_level_free_scratch": (i64, [vp]),
@@ -681,6 +685,65 @@ def streamgrad_trace(ctx: Context, states: Sequence[DevMF], nodes: np.ndarray, i
         out.append(o)
         fl.append(f)
     return out, fl
+
+
+def interpstream_fab(ctx: Context, loc: np.ndarray, loc_lo, fab: np.ndarray, fab_lo, dx, plo):
+    """pa_interpstream_fab: interpstream of sampleStreamlines_nd.f90 on one FAB.  loc [nl][nz][ny][nx] on loc_lo.. (X / Y / Z
+    first); fab [np][..] on fab_lo...  -> (strm [np][nz][ny][nx] -- NaN where nothing was written --, status 0 / 1 / 2)"""
+    loc = np.ascontiguousarray(loc, dtype=np.float64)
+    fab = np.ascontiguousarray(fab, dtype=np.float64)
+    lb, fb = DevBuf.from_numpy(ctx, loc), DevBuf.from_numpy(ctx, fab)
+    sb = DevBuf.from_numpy(ctx, np.full((fab.shape[0],) + loc.shape[1:], np.nan))
+    lf, ff, sf = _dev_fab(lb, loc_lo, loc.shape[1:], loc.shape[0]), _dev_fab(fb, fab_lo, fab.shape[1:], fab.shape[0]), _dev_fab(sb, loc_lo, loc.shape[1:], fab.shape[0])
+    st = C.c_int32(0)
+    ctx.check(ctx.lib.pa_interpstream_fab(ctx.h, C.byref(lf), loc.shape[0], C.byref(ff), fab.shape[0], C.byref(sf), _d3(dx), _d3(plo), C.byref(st)))
+    return sb.to_numpy(np.float64, (fab.shape[0],) + loc.shape[1:]), st.value
+
+
+def set_distance_fab(ctx: Context, loc: np.ndarray, loc_lo):
+    """pa_set_distance_fab: set_distance of sampleStreamlines_nd.f90.  loc [>= 3][nz][ny][nx] on loc_lo..  -> res [nz][ny][nx]"""
+    loc = np.ascontiguousarray(loc, dtype=np.float64)
+    lb = DevBuf.from_numpy(ctx, loc)
+    rb = DevBuf.from_numpy(ctx, np.full(loc.shape[1:], np.nan))
+    lf, rf = _dev_fab(lb, loc_lo, loc.shape[1:], loc.shape[0]), _dev_fab(rb, loc_lo, loc.shape[1:], 1)
+    ctx.check(ctx.lib.pa_set_distance_fab(ctx.h, C.byref(lf), C.byref(rf)))
+    return rb.to_numpy(np.float64, loc.shape[1:])
+
+
+def streamsample_run(ctx: Context, data: Sequence[DevMF], K: int, file_dx, plo, is_per, str_boxes, has_lines, bbox, xyz, ncout: int, dcomp: int = 4,
+                     with_xyzd: bool = True, out: Optional["DevBuf"] = None):
+    """pa_streamsample_run.  str_boxes[l] = [nb][6] Str boxes of level l; has_lines / bbox per level per box; xyz[l][b] = [3][nj][ni] path
+    coordinates.  out: the device result of an earlier pass (the next pass writes its components into it).  -> (out DevBuf,
+    per level per box [ncout][nj][ni] arrays, per level per box status)"""
+    nbox = np.array([len(b) for b in str_boxes], dtype=np.int32)
+    sb = np.ascontiguousarray(np.concatenate([np.asarray(b, np.int32).reshape(-1, 6) for b in str_boxes]), dtype=np.int32)
+    hl = np.ascontiguousarray(np.concatenate([np.asarray(h, np.int32).ravel() for h in has_lines]), dtype=np.int32)
+    bb = np.ascontiguousarray(np.concatenate([np.asarray(b, np.int32).reshape(-1, 6) for b in bbox]), dtype=np.int32)
+    flat = [np.asarray(x, np.float64) for per in xyz for x in per]
+    npts = [int(x[0].size) for x in flat]
+    xs = np.concatenate([x.reshape(3, -1).ravel() for x in flat])
+    xb = DevBuf.from_numpy(ctx, xs)
+    if out is None:
+        out = DevBuf.from_numpy(ctx, np.full(ncout * sum(npts), np.nan))
+    fdx = np.ascontiguousarray(np.asarray(file_dx, np.float64).reshape(-1, 3)[:len(data)])
+    fail = np.zeros(len(hl), dtype=np.int32)
+    ctx.check(ctx.lib.pa_streamsample_run(ctx.h, len(data), _handles(data), int(K), fdx.ctypes.data_as(C.POINTER(C.c_double)), _d3(plo), _i3(is_per),
+                                          nbox.ctypes.data_as(C.POINTER(C.c_int32)), sb.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          hl.ctypes.data_as(C.POINTER(C.c_int32)), bb.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(xb.ptr),
+                                          C.c_void_p(out.ptr), int(ncout), int(dcomp), int(bool(with_xyzd)), fail.ctypes.data_as(C.POINTER(C.c_int32))))
+    allv = out.to_numpy(np.float64, (ncout * sum(npts),))
+    res, st, g, o = [], [], 0, 0
+    for per in xyz:
+        r, s = [], []
+        for x in per:
+            n = int(np.asarray(x)[0].size)
+            r.append(allv[o:o + ncout * n].reshape((ncout,) + np.asarray(x).shape[1:]).copy())
+            s.append(int(fail[g]))
+            o += ncout * n
+            g += 1
+        res.append(r)
+        st.append(s)
+    return out, res, st
 
 
 def iso_merge(ctx: Context, fragments, ncomp: int):

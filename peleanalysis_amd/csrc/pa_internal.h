@@ -390,6 +390,20 @@ __device__ __forceinline__ int classify(const DLevelView& L, int i, int j, int k
 
 __host__ __device__ __forceinline__ int coarsen_idx(int i, int r) { return r == 2 ? (i >> 1) : ((i < 0) ? -((-i + r - 1) / r) : i / r); }  // floor
 
+// the 8-term trilinear sum of stream_nd.f90:197-205 (and sampleStreamlines_nd.f90:93-101, the same order); f(di, dj, dk) =
+// value at corner b + (di, dj, dk).  pa_streamgrad.hip and pa_streamsample.hip
+template <typename F>
+__device__ __forceinline__ double sg_sum(const double n[3], F f) {
+  return +n[0] * n[1] * n[2] * f(1, 1, 1)
+         + n[0] * (1.0 - n[1]) * n[2] * f(1, 0, 1)
+         + n[0] * n[1] * (1.0 - n[2]) * f(1, 1, 0)
+         + n[0] * (1.0 - n[1]) * (1.0 - n[2]) * f(1, 0, 0)
+         + (1.0 - n[0]) * n[1] * n[2] * f(0, 1, 1)
+         + (1.0 - n[0]) * (1.0 - n[1]) * n[2] * f(0, 0, 1)
+         + (1.0 - n[0]) * n[1] * (1.0 - n[2]) * f(0, 1, 0)
+         + (1.0 - n[0]) * (1.0 - n[1]) * (1.0 - n[2]) * f(0, 0, 0);
+}
+
 // amrex::poly_interp_coeff restated (Lagrange weights evaluated in fp64)
 __device__ __forceinline__ void poly_interp_coeff(double xInt, const double* x, int N, double* c) {
   for (int j = 0; j < N; ++j) {

@@ -50,19 +50,6 @@ __device__ __forceinline__ bool sg_locate(const SgGeom& G, const double x[3], co
   return ok;
 }
 
-// the 8-term sum of stream_nd.f90:197-205, in its order; f(di, dj, dk) = value at corner b + (di, dj, dk)
-template <typename F>
-__device__ __forceinline__ double sg_sum(const double n[3], F f) {
-  return +n[0] * n[1] * n[2] * f(1, 1, 1)
-         + n[0] * (1.0 - n[1]) * n[2] * f(1, 0, 1)
-         + n[0] * n[1] * (1.0 - n[2]) * f(1, 1, 0)
-         + n[0] * (1.0 - n[1]) * (1.0 - n[2]) * f(1, 0, 0)
-         + (1.0 - n[0]) * n[1] * n[2] * f(0, 1, 1)
-         + (1.0 - n[0]) * (1.0 - n[1]) * n[2] * f(0, 0, 1)
-         + (1.0 - n[0]) * n[1] * (1.0 - n[2]) * f(0, 1, 0)
-         + (1.0 - n[0]) * (1.0 - n[1]) * (1.0 - n[2]) * f(0, 0, 0);
-}
-
 // ntrpv of component m of F (bounds = F's box)
 __device__ __forceinline__ bool sg_ntrp(const SgGeom& G, const SgFab& F, int m, const double x[3], double& u) {
   int b[3];

@@ -280,10 +280,12 @@ inline PlotfileHeader read_header(const std::string& path, int dim_wanted = 3, b
 }
 
 // read component `comp` of the plotfile on level lev into component `dcomp` of dst (valid cells of
-// every dst box that lies inside a file box: dst boxes are the file's or a re-chop of them)
-inline void read_comp(const PlotfileHeader& H, int lev, int comp, HostMF& dst, int dcomp) {
+// every dst box that lies inside a file box: dst boxes are the file's or a re-chop of them); only: per file FAB, non-zero = read
+// it (null: all of them)
+inline void read_comp(const PlotfileHeader& H, int lev, int comp, HostMF& dst, int dcomp, const std::vector<char>* only = nullptr) {
   const LevelMeta& L = H.lev[lev];
   parallel_for(L.boxes.size(), [&](size_t fb) {  // file FABs are independent; destinations are disjoint valid regions
+    if (only && !(*only)[fb]) return;
     // does any dst box intersect this file box?
     std::vector<int> hits;
     for (size_t b = 0; b < dst.boxes.size(); ++b) {
@@ -360,6 +362,153 @@ inline void write_vismf_header(const std::string& file, const std::string& dname
   for (auto& m : mins) { for (double v : m) h << g17(v) << ","; h << "\n"; }
   h << "\n" << nb << "," << ncomp << "\n";
   for (auto& m : maxs) { for (double v : m) h << g17(v) << ","; h << "\n"; }
+}
+
+// ---- the streamFile directory of the stream-line tools (stream.cpp:2091-2226 writes it, sampleStreamlines.cpp:291-375 writes and
+// :434-501 reads it): Header (label, Nlev, names), Elements (nElts, nodesPerElt, the connectivity, then per level the non-empty
+// inside_nodes lists) and Level_<l>/Str_H + Str_D_00000 (VisMF, one process).  A Str FAB: box (0,-nRKh,0)..(n-1,nRKsteps-1-nRKh,0),
+// i = line, j = step (j = 0 the seed), component-major; a box without lines is the null box (0,0,0)..(0,0,0).
+struct StrFab {
+  Box3 box;
+  const double* data;  // ncomp * npts doubles
+  long long npts;
+};
+inline void write_stream_dir(std::string dir, const std::vector<std::string>& names, long long nElts, const std::vector<int32_t>& faceData,
+                             const std::vector<std::vector<std::vector<int32_t>>>& inside /* [lev][box] 1-based ids */, const std::vector<std::vector<StrFab>>& fabs) {
+  const int ncomp = (int)names.size(), nlev = (int)fabs.size();
+  if (!dir.empty() && dir.back() != '/') dir += '/';
+  ::mkdir(dir.c_str(), 0755);
+  {
+    std::ofstream h(dir + "/Header");
+    if (!h) Abort("Unable to create " + dir + "/Header");
+    h << "Oddball-multilevel-connected-data-format" << '\n' << nlev << '\n' << names.size() << '\n';
+    for (auto& n : names) h << n << '\n';
+  }
+  {
+    std::ofstream e(dir + "/Elements");
+    if (!e) Abort("Unable to create " + dir + "/Elements");
+    e << nElts << '\n' << (long long)faceData.size() / nElts << '\n';
+    for (int32_t v : faceData) e << v << " ";
+    e << '\n';
+    for (int lev = 0; lev < nlev; ++lev) {
+      int nz = 0;
+      for (auto& ids : inside[(size_t)lev]) nz += !ids.empty();
+      e << nz << '\n';
+      for (size_t j = 0; j < inside[(size_t)lev].size(); ++j) {
+        const auto& ids = inside[(size_t)lev][j];
+        if (ids.empty()) continue;
+        e << j << " " << ids.size();
+        for (int32_t v : ids) e << " " << v;
+        e << '\n';
+      }
+    }
+  }
+  for (int lev = 0; lev < nlev; ++lev) {
+    const std::string ldir = dir + "/Level_" + std::to_string(lev);
+    ::mkdir(ldir.c_str(), 0755);
+    const std::string dname = "Str_D_00000";
+    std::ofstream d(ldir + "/" + dname, std::ios::binary);
+    if (!d) Abort("Unable to create " + ldir + "/" + dname);
+    std::vector<std::string> bs;
+    std::vector<long long> offs;
+    std::vector<std::vector<double>> mins, maxs;
+    long long pos = 0;
+    for (const StrFab& F : fabs[(size_t)lev]) {
+      const std::string hdr = "FAB ((8, (64 11 52 0 1 12 0 1023)),(8, (8 7 6 5 4 3 2 1)))" + box_str(F.box) + ' ' + std::to_string(ncomp) + "\n";
+      offs.push_back(pos);
+      d.write(hdr.data(), (std::streamsize)hdr.size());
+      d.write((const char*)F.data, (std::streamsize)(8 * F.npts * ncomp));
+      pos += (long long)hdr.size() + 8 * F.npts * ncomp;
+      std::vector<double> mn((size_t)ncomp, 1e300), mx((size_t)ncomp, -1e300);
+      for (int c = 0; c < ncomp; ++c) minmax_run(F.data + (size_t)c * F.npts, F.npts, mn[(size_t)c], mx[(size_t)c]);
+      mins.push_back(mn);
+      maxs.push_back(mx);
+      bs.push_back(box_str(F.box));
+    }
+    if (!d) Abort("short write to " + ldir + "/" + dname);
+    write_vismf_header(ldir + "/Str_H", dname, ncomp, bs, offs, mins, maxs);
+  }
+}
+
+// read_ml_streamline_data (sampleStreamlines.cpp:434-501): every component of every Str FAB
+struct StreamDir {
+  std::string label;
+  std::vector<std::string> names;
+  long long nElts = 0, nodesPerElt = 0;
+  std::vector<int32_t> faceData;
+  std::vector<std::vector<std::vector<int32_t>>> inside;  // [lev][box] 1-based ids, empty for boxes without lines
+  std::vector<std::vector<Box3>> boxes;                   // [lev][box]
+  std::vector<std::vector<std::vector<double>>> data;     // [lev][box] ncomp * npts, component-major
+};
+inline StreamDir read_stream_dir(const std::string& dir) {
+  StreamDir S;
+  std::ifstream h(dir + "/Header");
+  if (!h) Abort("Unable to open " + dir + "/Header");
+  int nlev = 0, nc = 0;
+  h >> S.label >> nlev >> nc;
+  if (!h || nlev < 1 || nc < 3) Abort("bad streamline Header in " + dir);
+  S.names.resize((size_t)nc);
+  for (auto& n : S.names) h >> n;
+  std::ifstream e(dir + "/Elements");
+  if (!e) Abort("Unable to open " + dir + "/Elements");
+  e >> S.nElts >> S.nodesPerElt;
+  if (!e || S.nElts < 0 || S.nodesPerElt < 0) Abort("bad Elements in " + dir);
+  S.faceData.resize((size_t)(S.nElts * S.nodesPerElt));
+  for (auto& v : S.faceData) e >> v;
+  S.boxes.resize((size_t)nlev);
+  S.data.resize((size_t)nlev);
+  S.inside.resize((size_t)nlev);
+  for (int lev = 0; lev < nlev; ++lev) {
+    const std::string ldir = dir + "/Level_" + std::to_string(lev);
+    std::ifstream hf(ldir + "/Str_H");
+    if (!hf) Abort("Unable to open " + ldir + "/Str_H");
+    std::stringstream ss;
+    ss << hf.rdbuf();
+    const std::string txt = ss.str();
+    const size_t fod = txt.find("FabOnDisk");
+    const std::string blk = txt.substr(0, fod == std::string::npos ? txt.size() : fod);
+    size_t pos = blk.find('(');
+    Box3 bx;
+    while (parse_box(blk, pos, bx, 3)) S.boxes[(size_t)lev].push_back(bx);
+    for (size_t p = fod, b = 0; p != std::string::npos; p = txt.find("FabOnDisk", p + 9), ++b) {
+      std::stringstream ls(txt.substr(p + 10, 256));
+      std::string fn;
+      long long off;
+      ls >> fn >> off;
+      if (b >= S.boxes[(size_t)lev].size()) Abort("Str_H: more FabOnDisk lines than boxes in " + ldir);
+      std::ifstream f(ldir + "/" + fn, std::ios::binary);
+      if (!f) Abort("Unable to open " + ldir + "/" + fn);
+      f.seekg(off);
+      std::string hdr;
+      std::getline(f, hdr);
+      if (hdr.find("(8, (8 7 6 5 4 3 2 1))") == std::string::npos) Abort("unsupported Str FAB RealDescriptor in " + ldir + "/" + fn);
+      size_t q = hdr.find(")))");
+      Box3 fbx;
+      if (q == std::string::npos || !parse_box(hdr, q, fbx, 3)) Abort("bad FAB header in " + ldir + "/" + fn);
+      const int ncomp = std::atoi(hdr.c_str() + q);
+      if (ncomp != nc) Abort("Str FAB component count differs from the Header in " + ldir);
+      std::vector<double> v((size_t)(ncomp * fbx.numPts()));
+      f.read((char*)v.data(), (std::streamsize)(8 * v.size()));
+      if (!f) Abort("short read in " + ldir + "/" + fn);
+      S.data[(size_t)lev].push_back(std::move(v));
+    }
+    if (S.data[(size_t)lev].size() != S.boxes[(size_t)lev].size()) Abort("Str_H: FabOnDisk count does not match the boxes in " + ldir);
+    S.inside[(size_t)lev].resize(S.boxes[(size_t)lev].size());
+  }
+  for (int lev = 0; lev < nlev; ++lev) {  // the element distribution, after the levels are known (:477-498)
+    int nz = 0;
+    e >> nz;
+    for (int j = 0; j < nz; ++j) {
+      int bid = 0, n = 0;
+      e >> bid >> n;
+      if (!e || bid < 0 || bid >= (int)S.inside[(size_t)lev].size() || n < 0) Abort("bad element distribution in " + dir + "/Elements");
+      auto& ids = S.inside[(size_t)lev][(size_t)bid];
+      ids.resize((size_t)n);
+      for (auto& v : ids) e >> v;
+    }
+  }
+  if (!e) Abort("truncated " + dir + "/Elements");
+  return S;
 }
 
 // WriteMultiLevelPlotfile restated: valid cells of comps [0, names.size()) of each level's HostMF

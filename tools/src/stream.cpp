@@ -203,7 +203,6 @@ int main(int argc, char** argv) {
   // box membership (stream.cpp:710-766, setInsideNodes :141-216): 1-based ids per (level, file box), CSR over all boxes
   std::vector<int64_t> box_start(1, 0);
   std::vector<int32_t> ids;
-  std::vector<std::vector<int>> nInside(Nlev);
   for (int lev = 0; lev < Nlev; ++lev) {
     const pa::LevelMeta& L = H.lev[lev];
     double delta[3];
@@ -231,7 +230,6 @@ int main(int argc, char** argv) {
         for (int d = 0; d < 3; ++d) { q[(size_t)d] = H.prob_lo[d] + a[d] * delta[d]; q[(size_t)(3 + d)] = H.prob_lo[d] + (e[d] + 1.) * delta[d]; }
         fr.push_back(q);
       }
-      int cnt = 0;
       for (long long i = 0; i < nSeed; ++i) {
         bool isIn = true;
         for (int d = 0; d < 3; ++d) { const double x = nodes[(size_t)d * nSeed + i]; isIn = isIn && x >= lo[d] && x < hi[d]; }
@@ -240,9 +238,8 @@ int main(int argc, char** argv) {
           for (int d = 0; d < 3; ++d) { const double x = nodes[(size_t)d * nSeed + i]; inThis = inThis && x >= fr[n][(size_t)d] && x < fr[n][(size_t)(3 + d)]; }
           isIn = !inThis;
         }
-        if (isIn) { ids.push_back((int32_t)(i + 1)); ++cnt; }
+        if (isIn) ids.push_back((int32_t)(i + 1));
       }
-      nInside[(size_t)lev].push_back(cnt);
       box_start.push_back((int64_t)ids.size());
     }
   }
@@ -301,14 +298,15 @@ int main(int argc, char** argv) {
   if (cutHi) std::cerr << "Lines cut short on high end" << std::endl;
 
   // the Str FABs, level by level (stream.cpp:752-761): box (0,-nRKh,0)..(n-1,nRKsteps-1-nRKh,0), or the null box of zeros
-  struct StrFab { pa::Box3 box; const double* data; long long npts; };
-  std::vector<std::vector<StrFab>> fabs((size_t)Nlev);
+  std::vector<std::vector<pa::StrFab>> fabs((size_t)Nlev);
+  std::vector<std::vector<std::vector<int32_t>>> inside((size_t)Nlev);
   std::vector<double> zbuf((size_t)nCompStr, 0.0);
   {
     size_t g = 0;
     for (int lev = 0; lev < Nlev; ++lev)
       for (size_t b = 0; b < H.lev[lev].boxes.size(); ++b, ++g) {
         const long long n = box_start[g + 1] - box_start[g];
+        inside[(size_t)lev].emplace_back(ids.begin() + box_start[g], ids.begin() + box_start[g + 1]);
         if (n == 0) fabs[(size_t)lev].push_back({pa::Box3{{0, 0, 0}, {0, 0, 0}}, zbuf.data(), 1});
         else fabs[(size_t)lev].push_back({pa::Box3{{0, -nRKh, 0}, {(int)n - 1, nRKsteps - 1 - nRKh, 0}}, strm.data() + (size_t)box_start[g] * nRKsteps * nCompStr, n * nRKsteps});
       }
@@ -319,59 +317,8 @@ int main(int argc, char** argv) {
   if (nst > 0) {  // write_ml_streamline_data (stream.cpp:2091-2226), OLDFORMAT
     std::string dir;
     pp.get("streamFile", dir);
-    if (!dir.empty() && dir.back() != '/') dir += '/';
     std::cerr << "Writing the streamline data " << std::endl;
-    ::mkdir(dir.c_str(), 0755);
-    {
-      std::ofstream h(dir + "/Header");
-      if (!h) pa::Abort("Unable to create " + dir + "/Header");
-      h << "Oddball-multilevel-connected-data-format" << '\n' << Nlev << '\n' << strNames.size() << '\n';
-      for (auto& n : strNames) h << n << '\n';
-    }
-    {
-      std::ofstream e(dir + "/Elements");
-      if (!e) pa::Abort("Unable to create " + dir + "/Elements");
-      e << nElts << '\n' << (long long)faceData.size() / nElts << '\n';
-      for (int32_t v : faceData) e << v << " ";
-      e << '\n';
-      size_t g = 0;
-      for (int lev = 0; lev < Nlev; ++lev) {
-        int nz = 0;
-        for (int n : nInside[(size_t)lev]) nz += n > 0;
-        e << nz << '\n';
-        for (size_t j = 0; j < nInside[(size_t)lev].size(); ++j, ++g) {
-          if (nInside[(size_t)lev][j] == 0) continue;
-          e << j << " " << nInside[(size_t)lev][j];
-          for (int64_t q = box_start[g]; q < box_start[g + 1]; ++q) e << " " << ids[(size_t)q];
-          e << '\n';
-        }
-      }
-    }
-    for (int lev = 0; lev < Nlev; ++lev) {
-      const std::string ldir = dir + "/Level_" + std::to_string(lev);
-      ::mkdir(ldir.c_str(), 0755);
-      const std::string dname = "Str_D_00000";
-      std::ofstream d(ldir + "/" + dname, std::ios::binary);
-      if (!d) pa::Abort("Unable to create " + ldir + "/" + dname);
-      std::vector<std::string> bs;
-      std::vector<long long> offs;
-      std::vector<std::vector<double>> mins, maxs;
-      long long pos = 0;
-      for (const StrFab& F : fabs[(size_t)lev]) {
-        const std::string hdr = "FAB ((8, (64 11 52 0 1 12 0 1023)),(8, (8 7 6 5 4 3 2 1)))" + pa::box_str(F.box) + ' ' + std::to_string(nCompStr) + "\n";
-        offs.push_back(pos);
-        d.write(hdr.data(), (std::streamsize)hdr.size());
-        d.write((const char*)F.data, (std::streamsize)(8 * F.npts * nCompStr));
-        pos += (long long)hdr.size() + 8 * F.npts * nCompStr;
-        std::vector<double> mn((size_t)nCompStr, 1e300), mx((size_t)nCompStr, -1e300);
-        for (int c = 0; c < nCompStr; ++c) pa::minmax_run(F.data + (size_t)c * F.npts, F.npts, mn[(size_t)c], mx[(size_t)c]);
-        mins.push_back(mn);
-        maxs.push_back(mx);
-        bs.push_back(pa::box_str(F.box));
-      }
-      if (!d) pa::Abort("short write to " + ldir + "/" + dname);
-      pa::write_vismf_header(ldir + "/Str_H", dname, nCompStr, bs, offs, mins, maxs);
-    }
+    pa::write_stream_dir(dir, strNames, nElts, faceData, inside, fabs);
     std::cerr << "...done writing the streamline data " << std::endl;
   } else {  // dump_ml_streamline_data (stream.cpp:2228-2302), one process
     std::string dir;
@@ -379,7 +326,7 @@ int main(int argc, char** argv) {
     ::mkdir(dir.c_str(), 0755);
     bool will_write = false;
     for (auto& L : fabs)
-      for (const StrFab& F : L) will_write = will_write || F.box.lo[1] != 0 || F.box.hi[0] != 0 || F.box.hi[1] != 0;
+      for (const pa::StrFab& F : L) will_write = will_write || F.box.lo[1] != 0 || F.box.hi[0] != 0 || F.box.hi[1] != 0;
     if (will_write) {
       std::ofstream o(dir + "/str_00000.dat");
       if (!o) pa::Abort("Unable to create " + dir + "/str_00000.dat");
@@ -387,7 +334,7 @@ int main(int argc, char** argv) {
       for (auto& n : strNames) o << n << " ";
       o << '\n';
       for (auto& L : fabs)
-        for (const StrFab& F : L) {
+        for (const pa::StrFab& F : L) {
           if (F.box.lo[1] == 0 && F.box.hi[0] == 0 && F.box.hi[1] == 0) continue;  // equals the null box
           const int n = F.box.hi[0] + 1, J = F.box.hi[1] - F.box.lo[1] + 1;
           for (int i = 0; i < n; ++i) {
