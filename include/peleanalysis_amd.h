@@ -500,6 +500,57 @@ int pa_streamsample_run(pa_ctx*, int nlev, pa_mf* const* data, int32_t K, const 
 /* hipMemGetInfo of the context's device: the tools size their passes by it */
 int pa_device_mem_info(pa_ctx*, int64_t* free_bytes, int64_t* total_bytes);
 
+/* ------------------------------------------------------------- binned statistics (jpdf.cpp / conditionalMean.cpp)
+ * One accumulator object (pa_hist) lives across the levels of a plotfile; the add_level calls take ONE level at a time -- its data,
+ * the next finer level (boxes only; NULL: nothing is covered) and the refinement ratio -- so only one level's components have to be
+ * resident.  A cell counts when its refined image has no owner on `finer` (jpdf.cpp:373-387, :472; conditionalMean.cpp:246-258, :267).
+ * NUMERICS: the reference adds cell after cell in double precision; here every sum is a 192-bit fixed-point integer (quantum
+ * 2^-157 x the power of two above the magnitude declared at begin) added with 64-bit integer atomics and rounded ONCE when read.
+ * Bin indices, counts, hits, minima and maxima are exact; a sum S of n terms t satisfies |S - sum t| <= 2^-53 |sum t| (+ n quanta
+ * for terms below 2^-105 of the declared magnitude), the same bits on every run and for every tiling or box order of the level.
+ * A term larger than twice the declared magnitude, or not finite, makes the read call fail.  One rank; 3-D levels.
+ * add_level is asynchronous on the context's stream unless it returns counts; begin and read are synchronous. */
+#define PA_STATS_MAXV 8
+typedef struct pa_hist pa_hist;
+typedef struct {
+  int32_t nload;            /* loaded variables: components 0 .. nload-1 of the multifab */
+  int32_t do_stoichiometry; /* one more variable, index nload: 0.5 * sumH / sumO over the loaded ones (jpdf.cpp:410-418) */
+  double  hlist[PA_STATS_MAXV], olist[PA_STATS_MAXV];
+  double  vmin[PA_STATS_MAXV], vmax[PA_STATS_MAXV]; /* axis of every variable (jpdf.cpp:297-326); vmax == vmin is refused */
+  int32_t do_conditioning;  /* 0, 1: c, 2: c (1 - c) (jpdf.cpp:476-487) */
+  int32_t cvar, norm_cval;
+  double  cnorm_min, cnorm_max, cmin, cmax;
+  int32_t uncombined;       /* 1: the plain kernel, one set of global atomics per cell (measurement; identical bits) */
+} pa_jpdf_params;
+/* AmrData::MinMax of several components of one level in one launch (jpdf.cpp:297-306): every valid cell, cells covered by a finer
+ * level included.  ncomps <= 16.  Synchronous. */
+int pa_minmax_comps_level(pa_ctx*, const pa_mf* s, int ncomps, const int32_t* comps, double* mn, double* mx);
+/* jpdf.cpp:328-337: the three accumulators bin / binX1 / binX2 of all nvars (nvars - 1) / 2 pairs, pair order as the loops at :427-428 */
+pa_hist* pa_jpdf_create(pa_ctx*, int nvars, int nbins);
+/* zero the accumulators for a new plotfile and fix their scales: vol_max = the largest cell volume that will be added (level 0's),
+ * vabs[v] >= |value| of variable v (max(|vMin|, |vMax|) of the data; 2 for the stoichiometry) */
+int pa_jpdf_begin(pa_ctx*, pa_hist*, double vol_max, const double* vabs /* [nvars] */);
+/* jpdf.cpp:440-522 for one level: ONE pass over the cells bins all pairs (up to 6 per pass).  Bin index (int)(nBins*(v-vMin)/(vMax-vMin));
+ * a quotient >= nBins (+inf too) clamps high and counts, <= -1 clamps low and counts, NaN skips the cell for that pair and counts.
+ * outside: host [npairs][4] = v1l v1g v2l v2g of THIS level (:516-521), nan_cells: host [npairs]; either may be NULL. */
+int pa_jpdf_add_level(pa_ctx*, pa_hist*, const pa_mf* vars, const pa_level* finer, int ratio, double vol, const pa_jpdf_params*,
+                      int64_t* outside, int64_t* nan_cells);
+/* raw sums (before jpdf.cpp:571-589), [npairs][nbins * nbins] each, bin v1i * nbins + v2i */
+int pa_jpdf_read(pa_ctx*, const pa_hist*, double* bin, double* binx1, double* binx2);
+/* conditionalMean.cpp:97-106: binHits (64-bit here), binVals, binValsSq and, with_minmax, binMinVals / binMaxVals; navg <= 8 per object */
+pa_hist* pa_condmean_create(pa_ctx*, int navg, int nbins, int with_minmax);
+/* zero + scales: weight_max = the largest cell weight (level 0's), vabs[a] >= |value| of averaged component a */
+int pa_condmean_begin(pa_ctx*, pa_hist*, int64_t weight_max, const double* vabs /* [navg] */);
+/* conditionalMean.cpp:260-296 for one level: comps holds the bin component first, then the navg averaged ones; domain = the bounds
+ * box in this level's index space (:183-191, :226); a cell with binMin <= binVal < binMax goes to bin (int)(nBins*(binVal-binMin)/
+ * (binMax-binMin)) with sums weight*val and (weight*val)*val; an index outside [0, nBins) is the reference's "Bad bin" abort: the
+ * read call fails.  uncombined != 0: the plain kernel (measurement; identical bits). */
+int pa_condmean_add_level(pa_ctx*, pa_hist*, const pa_mf* comps, const pa_level* finer, int ratio, const pa_box* domain,
+                          int64_t weight, double bin_min, double bin_max, int uncombined);
+/* hits [nbins]; sum, sumsq, mn, mx [nbins][navg] (mn / mx may be NULL without with_minmax; 0 in empty bins) */
+int pa_condmean_read(pa_ctx*, const pa_hist*, int64_t* hits, double* sum, double* sumsq, double* mn, double* mx);
+void pa_hist_destroy(pa_hist*);
+
 /* ------------------------------------------------------------ tool pipelines
  * The level loops of the tool mains, operating on device-resident MultiFabs.
  * levels/state/out are arrays of nlev pointers, coarse first. */

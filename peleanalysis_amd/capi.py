@@ -55,6 +55,12 @@ class PaIsoFrag(C.Structure):
     _fields_ = [("verts", C.c_void_p), ("nvert", C.c_int64), ("tris", C.c_void_p), ("ntri", C.c_int64)]
 
 
+class PaJpdfParams(C.Structure):
+    _fields_ = [("nload", C.c_int32), ("do_stoichiometry", C.c_int32), ("hlist", C.c_double * 8), ("olist", C.c_double * 8), ("vmin", C.c_double * 8),
+                ("vmax", C.c_double * 8), ("do_conditioning", C.c_int32), ("cvar", C.c_int32), ("norm_cval", C.c_int32), ("cnorm_min", C.c_double),
+                ("cnorm_max", C.c_double), ("cmin", C.c_double), ("cmax", C.c_double), ("uncombined", C.c_int32)]
+
+
 class PaSdfGrid(C.Structure):
     _fields_ = [("ntri", C.c_int64), ("tri", C.c_void_p), ("nvert", C.c_int64), ("x", C.c_void_p), ("origin", C.c_float * 3), ("dx", C.c_float),
                 ("n", C.c_int32 * 3), ("phi", C.c_void_p)]
@@ -184,6 +190,16 @@ def load_library() -> C.CDLL:
         "pa_set_distance_fab": (C.c_int, [vp, C.POINTER(PaFab), C.POINTER(PaFab)]),
         "pa_streamsample_run": (C.c_int, [vp, C.c_int, C.POINTER(vp), i32, pdbl, pdbl, pi32, pi32, pi32, pi32, pi32, vp, vp, i32, i32, i32, pi32]),
         "pa_device_mem_info": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
+        "pa_minmax_comps_level": (C.c_int, [vp, vp, C.c_int, pi32, pdbl, pdbl]),
+        "pa_jpdf_create": (vp, [vp, C.c_int, C.c_int]),
+        "pa_jpdf_begin": (C.c_int, [vp, vp, dbl, pdbl]),
+        "pa_jpdf_add_level": (C.c_int, [vp, vp, vp, vp, C.c_int, dbl, C.POINTER(PaJpdfParams), C.POINTER(i64), C.POINTER(i64)]),
+        "pa_jpdf_read": (C.c_int, [vp, vp, pdbl, pdbl, pdbl]),
+        "pa_condmean_create": (vp, [vp, C.c_int, C.c_int, C.c_int]),
+        "pa_condmean_begin": (C.c_int, [vp, vp, i64, pdbl]),
+        "pa_condmean_add_level": (C.c_int, [vp, vp, vp, vp, C.c_int, C.POINTER(PaBox), i64, dbl, dbl, C.c_int]),
+        "pa_condmean_read": (C.c_int, [vp, vp, C.POINTER(i64), pdbl, pdbl, pdbl, pdbl]),
+        "pa_hist_destroy": (None, [vp]),
         "pa_smooth_last": (C.c_int, [vp, C.POINTER(C.c_int), pdbl]),
         "pa_curvature_last_path": (C.c_int, [vp]),
         "pa_level_free_scratch": (i64, [vp]),
@@ -810,3 +826,108 @@ def mc_level(ctx: Context, state: "DevMF", mask: "DevMF", loops, isocomp: int, i
         out.append((V[ov:ov + nv[b]], K[ov:ov + nv[b]], T[ot:ot + nt[b]]))
         ov += nv[b]; ot += nt[b]
     return out
+
+
+# ----------------------------------------------------------------------------- binned statistics (jpdf.cpp / conditionalMean.cpp)
+def minmax_comps_level(ctx: Context, mf: "DevMF", comps):
+    """pa_minmax_comps_level: (min, max) arrays over every valid cell of the level for the listed components, one launch"""
+    c = np.ascontiguousarray(comps, dtype=np.int32)
+    mn, mx = np.zeros(len(c)), np.zeros(len(c))
+    pd = C.POINTER(C.c_double)
+    ctx.check(ctx.lib.pa_minmax_comps_level(ctx.h, mf.h, len(c), c.ctypes.data_as(C.POINTER(C.c_int32)), mn.ctypes.data_as(pd), mx.ctypes.data_as(pd)))
+    return mn, mx
+
+
+def jpdf_params(nload, vmin, vmax, do_stoichiometry=False, hlist=None, olist=None, do_conditioning=0, cvar=0, norm_cval=0, cnorm_min=0.0,
+                cnorm_max=1.0, cmin=0.0, cmax=1.0, uncombined=False) -> PaJpdfParams:
+    """pa_jpdf_params: the keys of jpdf.cpp:82-243 that the cell loop reads"""
+    p = PaJpdfParams()
+    p.nload, p.do_stoichiometry = int(nload), int(bool(do_stoichiometry))
+    for v, x in enumerate(hlist if hlist is not None else []):
+        p.hlist[v] = float(x)
+    for v, x in enumerate(olist if olist is not None else []):
+        p.olist[v] = float(x)
+    for v, (a, b) in enumerate(zip(vmin, vmax)):
+        p.vmin[v], p.vmax[v] = float(a), float(b)
+    p.do_conditioning, p.cvar, p.norm_cval = int(do_conditioning), int(cvar), int(norm_cval)
+    p.cnorm_min, p.cnorm_max, p.cmin, p.cmax = float(cnorm_min), float(cnorm_max), float(cmin), float(cmax)
+    p.uncombined = int(bool(uncombined))
+    return p
+
+
+class _Hist:
+    def close(self):
+        """pa_hist_destroy (no finaliser, as for levels and multifabs)"""
+        if self.h:
+            self.ctx.lib.pa_hist_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class JpdfAcc(_Hist):
+    """the bin / binX1 / binX2 accumulators of all pairs of nvars variables (pa_jpdf_*)"""
+
+    def __init__(self, ctx: Context, nvars: int, nbins: int):
+        self.ctx, self.nvars, self.nbins, self.npairs = ctx, int(nvars), int(nbins), int(nvars) * (int(nvars) - 1) // 2
+        self.h = ctx.lib.pa_jpdf_create(ctx.h, int(nvars), int(nbins))
+        if not self.h:
+            raise PaError(ctx.lib.pa_last_error(ctx.h).decode())
+
+    def begin(self, vol_max: float, vabs):
+        a = np.ascontiguousarray(vabs, dtype=np.float64)
+        assert len(a) == self.nvars
+        self.ctx.check(self.ctx.lib.pa_jpdf_begin(self.ctx.h, self.h, float(vol_max), a.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def add_level(self, mf: "DevMF", finer: Optional["DevLevel"], ratio: int, vol: float, params: PaJpdfParams):
+        """-> (outside [npairs][4] = v1l v1g v2l v2g, nan_cells [npairs]) of this level"""
+        out, nan = np.zeros((self.npairs, 4), np.int64), np.zeros(self.npairs, np.int64)
+        pi = C.POINTER(C.c_int64)
+        self.ctx.check(self.ctx.lib.pa_jpdf_add_level(self.ctx.h, self.h, mf.h, finer.h if finer is not None else None, int(ratio), float(vol),
+                                                      C.byref(params), out.ctypes.data_as(pi), nan.ctypes.data_as(pi)))
+        return out, nan
+
+    def read(self):
+        """raw sums -> bin, binX1, binX2, each [npairs][nbins][nbins] (v1i, v2i)"""
+        sh = (self.npairs, self.nbins, self.nbins)
+        b, x1, x2 = np.zeros(sh), np.zeros(sh), np.zeros(sh)
+        pd = C.POINTER(C.c_double)
+        self.ctx.check(self.ctx.lib.pa_jpdf_read(self.ctx.h, self.h, b.ctypes.data_as(pd), x1.ctypes.data_as(pd), x2.ctypes.data_as(pd)))
+        return b, x1, x2
+
+
+class CondMeanAcc(_Hist):
+    """binHits / binVals / binValsSq (/ binMinVals / binMaxVals) of conditionalMean.cpp (pa_condmean_*)"""
+
+    def __init__(self, ctx: Context, navg: int, nbins: int, with_minmax: bool = False):
+        self.ctx, self.navg, self.nbins, self.with_minmax = ctx, int(navg), int(nbins), bool(with_minmax)
+        self.h = ctx.lib.pa_condmean_create(ctx.h, int(navg), int(nbins), int(bool(with_minmax)))
+        if not self.h:
+            raise PaError(ctx.lib.pa_last_error(ctx.h).decode())
+
+    def begin(self, weight_max: int, vabs):
+        a = np.ascontiguousarray(vabs, dtype=np.float64)
+        assert len(a) == self.navg
+        self.ctx.check(self.ctx.lib.pa_condmean_begin(self.ctx.h, self.h, int(weight_max), a.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def add_level(self, mf: "DevMF", finer: Optional["DevLevel"], ratio: int, domain, weight: int, bin_min: float, bin_max: float, uncombined: bool = False):
+        """mf: bin component first, then the averaged ones; domain: (lo0, lo1, lo2, hi0, hi1, hi2) in the level's index space"""
+        bx = PaBox()
+        for d in range(3):
+            bx.lo[d], bx.hi[d] = int(domain[d]), int(domain[3 + d])
+        self.ctx.check(self.ctx.lib.pa_condmean_add_level(self.ctx.h, self.h, mf.h, finer.h if finer is not None else None, int(ratio), C.byref(bx),
+                                                          int(weight), float(bin_min), float(bin_max), int(bool(uncombined))))
+
+    def read(self):
+        """-> hits [nbins] int64, sum, sumsq [nbins][navg], mn, mx [nbins][navg] or None"""
+        sh = (self.nbins, self.navg)
+        hits, s, s2 = np.zeros(self.nbins, np.int64), np.zeros(sh), np.zeros(sh)
+        mn, mx = (np.zeros(sh), np.zeros(sh)) if self.with_minmax else (None, None)
+        pd = C.POINTER(C.c_double)
+        self.ctx.check(self.ctx.lib.pa_condmean_read(self.ctx.h, self.h, hits.ctypes.data_as(C.POINTER(C.c_int64)), s.ctypes.data_as(pd), s2.ctypes.data_as(pd),
+                                                     mn.ctypes.data_as(pd) if mn is not None else None, mx.ctypes.data_as(pd) if mx is not None else None))
+        return hits, s, s2, mn, mx

@@ -364,6 +364,32 @@ inline void write_vismf_header(const std::string& file, const std::string& dname
   for (auto& m : maxs) { for (double v : m) h << g17(v) << ","; h << "\n"; }
 }
 
+// FArrayBox::writeOn of a FAB with doubles on an arbitrary box (jpdf.cpp:700-720: the .fab output; the FAB of its 2-D "plotfile"):
+// the header line, then ncomp * numPts doubles, component-major.  Returns the bytes written.
+inline long long write_fab(std::ostream& os, const Box3& b, int ncomp, const double* data) {
+  const std::string hdr = "FAB ((8, (64 11 52 0 1 12 0 1023)),(8, (8 7 6 5 4 3 2 1)))" + box_str(b) + ' ' + std::to_string(ncomp) + "\n";
+  os.write(hdr.data(), (std::streamsize)hdr.size());
+  os.write((const char*)data, (std::streamsize)(sizeof(double) * (size_t)ncomp * (size_t)b.numPts()));
+  return (long long)hdr.size() + 8LL * ncomp * b.numPts();
+}
+
+// The hand-written Header of jpdf.cpp's 2-D "plotfile" of bins (jpdf.cpp:778-838): 2 * npairs components on ONE grid of nBins x nBins
+// cells over the unit square, followed by one "vMin vMax" line per variable (the axes); numbers with precision 15
+inline void write_jpdf_header(const std::string& file, const std::vector<std::string>& pairNames, double time, int nBins,
+                              const std::vector<double>& vMin, const std::vector<double>& vMax) {
+  std::ofstream os(file);
+  if (!os) Abort("Unable to create " + file);
+  os.precision(15);
+  os << "NavierStokes-V1.1" << '\n' << 2 * pairNames.size() << '\n';
+  for (const std::string& n : pairNames) os << n << '\n';
+  for (const std::string& n : pairNames) os << n << " (log)" << '\n';
+  os << "2" << '\n' << time << '\n' << "0" << '\n' << "0 0\n" << "1 1\n" << '\n';
+  os << "((0,0) (" << nBins - 1 << "," << nBins - 1 << ") (0,0))" << '\n' << "0" << '\n';
+  os << 1.0 / nBins << " " << 1.0 / nBins << '\n' << "0\n0\n";
+  os << "0 1 " << time << '\n' << "0" << '\n' << "0 1\n" << "0 1\n" << "Level_0/Cell" << '\n';
+  for (size_t v = 0; v < vMin.size(); ++v) os << vMin[v] << " " << vMax[v] << '\n';
+}
+
 // ---- the streamFile directory of the stream-line tools (stream.cpp:2091-2226 writes it, sampleStreamlines.cpp:291-375 writes and
 // :434-501 reads it): Header (label, Nlev, names), Elements (nElts, nodesPerElt, the connectivity, then per level the non-empty
 // inside_nodes lists) and Level_<l>/Str_H + Str_D_00000 (VisMF, one process).  A Str FAB: box (0,-nRKh,0)..(n-1,nRKsteps-1-nRKh,0),
