@@ -551,6 +551,50 @@ int pa_condmean_add_level(pa_ctx*, pa_hist*, const pa_mf* comps, const pa_level*
 int pa_condmean_read(pa_ctx*, const pa_hist*, int64_t* hits, double* sum, double* sumsq, double* mn, double* mx);
 void pa_hist_destroy(pa_hist*);
 
+/* ------------------------------------------------------------- stream tubes (streamTubeStats.cpp)
+ * The three lines through the nodes of a surface triangle bound a stream tube; between consecutive line points it is a wedge.
+ * DATA LAYOUT: the Str FABs of a streamSampleFile, all levels and boxes back to back (box g after the boxes before it): a buffer of
+ * ncomp components holds box g at ncomp * off_g doubles, component-major, i (line in box) fastest, then j -- what
+ * pa_streamsample_run takes for xyz.  xyz = such a buffer of the 3 coordinates; data = one of the components the call names.
+ * NUMERICS: a thread owns a triangle or a line from its first point to its last; every expression keeps the reference's association
+ * and every sum its order (j, then the CSR's column order), without floating-point atomics: the results are the serial code's bits
+ * for any grouping of the components.  All calls are synchronous; arrays are device memory unless called "host".
+ *
+ * The tables of one stream directory: box_desc host [nbt][4] = (ni, nj, jlo, off_g) of every Str box of every level (build_nodeMap
+ * :1256-1281 needs them flat); node_table host [nNodes][2] = (box g, line i) of node id n + 1; faceData host [nElts][3], 1-based.
+ * Node ids outside 1 .. nNodes, boxes or lines out of range: NULL with pa_last_error set (the reference asserts in debug builds). */
+typedef struct pa_tube pa_tube;
+pa_tube* pa_tube_create(pa_ctx*, int32_t nbt, const int64_t* box_desc, int64_t nNodes, const int32_t* node_table, int64_t nElts,
+                        const int32_t* faceData);
+void pa_tube_destroy(pa_tube*);
+/* The element loop of streamTubeStats.cpp:650-699 with wedge_volume_int / tetVol / wedge_surf_area (:850-873, :1003-1254): for every
+ * triangle the wedges j = jlo .. jlo + nPtsOnStr - 2 in order; components 0 .. K-1 of data are integrated.  ints_raw [K][nElts] =
+ * the sums (what :693-694 totals), ints_per_area [K][nElts] = the sums / area (:696-699).  with_geom != 0 also writes vol, area (the
+ * triangle at j = 0) and wa [nElts] (:663-685; wa = area_wtAvg of component 0 of THIS call, 0 when K == 0): a caller that passes the
+ * components in groups asks for them with the first group.  Every box with lines must hold j = 0 and the swept range (the reference
+ * indexes without a check): checked on the host before any launch. */
+int pa_tube_wedges(pa_ctx*, pa_tube*, const double* xyz, const double* data, int32_t K, int32_t jlo, int32_t nPtsOnStr,
+                   int32_t with_geom, double* vol, double* area, double* wa, double* ints_raw, double* ints_per_area);
+/* max_grad (:876-952) of component comp of data (ncomp components) along every line, over the box's whole j range: gradmax [nNodes].
+ * use_eps == 0: a gradient counts across segments with L > maxs, the longest segment (the reference's test); != 0: L > 1.e-4 * maxs. */
+int pa_tube_lines(pa_ctx*, pa_tube*, const double* xyz, const double* data, int32_t ncomp, int32_t comp, int32_t use_eps,
+                  double* gradmax);
+/* peak_val (:955-1001): the first maximum (strict >) of component pcomp along every line; peak_samples [nsample][nNodes] = the
+ * components sample_comps (host, nsample <= 32) there; ok [nNodes] int32 = 0 when it sits at the first or last point of the line */
+int pa_tube_peaks(pa_ctx*, pa_tube*, const double* data, int32_t ncomp, int32_t pcomp, int32_t nsample, const int32_t* sample_comps,
+                  double* peak_samples, int32_t* ok);
+/* node values to elements (:724-753): out [nv][nElts] = (a + b + c) / 3. of vals [nv][nNodes] at the element's nodes in order */
+int pa_tube_node_means(pa_ctx*, pa_tube*, int32_t nv, const double* vals, double* out);
+/* :739-742: out [nElts] = 1.0 where ok (int32 [nNodes]) holds at all three nodes, else 0.0 */
+int pa_tube_node_all(pa_ctx*, pa_tube*, const int32_t* ok, double* out);
+/* :703-713: out [nElts] = the values of component comp at the surface (j = 0) of the three nodes, summed from 0 in node order, / 3 */
+int pa_tube_node_avg(pa_ctx*, pa_tube*, const double* data, int32_t ncomp, int32_t comp, double* out);
+/* smoothVals (:274-298) nSmooth times over ping-pong buffers, neighbours from buildNodeNeighbors (:196-235): every other element that
+ * shares a node, ascending, built on the device at the first call and kept with the tube.  nSmooth <= 0 copies vals.  out != vals. */
+int pa_tube_smooth(pa_ctx*, pa_tube*, const double* vals, const double* area, int32_t nSmooth, double* out);
+/* the neighbour lists as CSR, to the host: *nnz always; rowptr [nElts + 1] and cols [*nnz] where not NULL (tests) */
+int pa_tube_neighbors(pa_ctx*, pa_tube*, int64_t* nnz, int64_t* rowptr, int32_t* cols);
+
 /* ------------------------------------------------------------ tool pipelines
  * The level loops of the tool mains, operating on device-resident MultiFabs.
  * levels/state/out are arrays of nlev pointers, coarse first. */

@@ -200,6 +200,16 @@ def load_library() -> C.CDLL:
         "pa_condmean_add_level": (C.c_int, [vp, vp, vp, vp, C.c_int, C.POINTER(PaBox), i64, dbl, dbl, C.c_int]),
         "pa_condmean_read": (C.c_int, [vp, vp, C.POINTER(i64), pdbl, pdbl, pdbl, pdbl]),
         "pa_hist_destroy": (None, [vp]),
+        "pa_tube_create": (vp, [vp, i32, C.POINTER(i64), i64, pi32, i64, pi32]),
+        "pa_tube_destroy": (None, [vp]),
+        "pa_tube_wedges": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "pa_tube_lines": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp]),
+        "pa_tube_peaks": (C.c_int, [vp, vp, vp, i32, i32, i32, pi32, vp, vp]),
+        "pa_tube_node_means": (C.c_int, [vp, vp, i32, vp, vp]),
+        "pa_tube_node_all": (C.c_int, [vp, vp, vp, vp]),
+        "pa_tube_node_avg": (C.c_int, [vp, vp, vp, i32, i32, vp]),
+        "pa_tube_smooth": (C.c_int, [vp, vp, vp, vp, i32, vp]),
+        "pa_tube_neighbors": (C.c_int, [vp, vp, C.POINTER(i64), C.POINTER(i64), pi32]),
         "pa_smooth_last": (C.c_int, [vp, C.POINTER(C.c_int), pdbl]),
         "pa_curvature_last_path": (C.c_int, [vp]),
         "pa_level_free_scratch": (i64, [vp]),
@@ -760,6 +770,107 @@ def streamsample_run(ctx: Context, data: Sequence[DevMF], K: int, file_dx, plo, 
         res.append(r)
         st.append(s)
     return out, res, st
+
+
+def _dev(ctx: Context, a) -> "DevBuf":
+    """a DevBuf as it is, a host array uploaded (at least 8 bytes, so that an empty array still has an address)"""
+    if isinstance(a, DevBuf):
+        return a
+    a = np.ascontiguousarray(a)
+    return DevBuf.from_numpy(ctx, a) if a.nbytes else DevBuf(ctx, 8)
+
+
+class Tube:
+    """pa_tube (streamTubeStats.cpp): the tables of one stream directory and the calls on them.  box_desc [nbt][4] = (ni, nj, jlo,
+    offset in points) of every Str box of every level, node_table [nNodes][2] = (box, line) of node id n + 1, face = the 1-based
+    connectivity.  xyz / data arguments: flat buffers in the layout of Tube.flat, host arrays (uploaded) or DevBufs."""
+
+    def __init__(self, ctx: Context, box_desc, node_table, face):
+        self.ctx = ctx
+        self.box = np.ascontiguousarray(box_desc, dtype=np.int64).reshape(-1, 4)
+        self.node = np.ascontiguousarray(node_table, dtype=np.int32).reshape(-1, 2)
+        self.face = np.ascontiguousarray(face, dtype=np.int32).reshape(-1, 3)
+        self.nNodes, self.nElts = len(self.node), len(self.face)
+        self.h = ctx.lib.pa_tube_create(ctx.h, len(self.box), self.box.ctypes.data_as(C.POINTER(C.c_int64)), self.nNodes,
+                                        self.node.ctypes.data_as(C.POINTER(C.c_int32)), self.nElts, self.face.ctypes.data_as(C.POINTER(C.c_int32)))
+        if not self.h:
+            raise PaError(ctx.lib.pa_last_error(ctx.h).decode())
+
+    @staticmethod
+    def flat(fabs) -> np.ndarray:
+        """fabs[g] = [ncomp][nj][ni] of every box -> box g at ncomp * off_g doubles, component-major, i fastest, then j"""
+        return np.concatenate([np.asarray(a, np.float64).ravel() for a in fabs]) if len(fabs) else np.zeros(0)
+
+    def _out(self, n):
+        return DevBuf(self.ctx, max(8, 8 * int(n)))
+
+    def wedges(self, xyz, data, K: int, jlo: int, nPtsOnStr: int, with_geom: bool = True):
+        """pa_tube_wedges -> (vol, area, wa [nElts] or None without with_geom, ints_raw [K][nElts], ints_per_area [K][nElts])"""
+        E = self.nElts
+        x, d = _dev(self.ctx, xyz), _dev(self.ctx, data)
+        vol, area, wa, raw, per = self._out(E), self._out(E), self._out(E), self._out(K * E), self._out(K * E)
+        self.ctx.check(self.ctx.lib.pa_tube_wedges(self.ctx.h, self.h, x.ptr, d.ptr, int(K), int(jlo), int(nPtsOnStr), int(bool(with_geom)), vol.ptr, area.ptr,
+                                                   wa.ptr, raw.ptr, per.ptr))
+        g = tuple(b.to_numpy(np.float64, (E,)) for b in (vol, area, wa)) if with_geom else (None, None, None)
+        return g + (raw.to_numpy(np.float64, (K, E)), per.to_numpy(np.float64, (K, E)))
+
+    def lines(self, xyz, data, ncomp: int, comp: int, use_eps: bool = False) -> np.ndarray:
+        """pa_tube_lines -> gradmax [nNodes]"""
+        x, d, o = _dev(self.ctx, xyz), _dev(self.ctx, data), self._out(self.nNodes)
+        self.ctx.check(self.ctx.lib.pa_tube_lines(self.ctx.h, self.h, x.ptr, d.ptr, int(ncomp), int(comp), int(bool(use_eps)), o.ptr))
+        return o.to_numpy(np.float64, (self.nNodes,))
+
+    def peaks(self, data, ncomp: int, pcomp: int, sample_comps=()):
+        """pa_tube_peaks -> (peak_samples [nsample][nNodes], ok [nNodes] bool)"""
+        sc = np.ascontiguousarray(sample_comps, dtype=np.int32)
+        d, o, k = _dev(self.ctx, data), self._out(len(sc) * self.nNodes), self._out(self.nNodes)
+        self.ctx.check(self.ctx.lib.pa_tube_peaks(self.ctx.h, self.h, d.ptr, int(ncomp), int(pcomp), len(sc), sc.ctypes.data_as(C.POINTER(C.c_int32)), o.ptr, k.ptr))
+        return o.to_numpy(np.float64, (len(sc), self.nNodes)), k.to_numpy(np.int32, (self.nNodes,)) != 0
+
+    def node_means(self, vals) -> np.ndarray:
+        """pa_tube_node_means: vals [nv][nNodes] -> [nv][nElts]"""
+        vals = np.ascontiguousarray(vals, dtype=np.float64).reshape(-1, self.nNodes)
+        v, o = _dev(self.ctx, vals), self._out(len(vals) * self.nElts)
+        self.ctx.check(self.ctx.lib.pa_tube_node_means(self.ctx.h, self.h, len(vals), v.ptr, o.ptr))
+        return o.to_numpy(np.float64, (len(vals), self.nElts))
+
+    def node_all(self, ok) -> np.ndarray:
+        """pa_tube_node_all: ok [nNodes] -> [nElts] 1.0 / 0.0"""
+        k, o = _dev(self.ctx, np.ascontiguousarray(ok, dtype=np.int32)), self._out(self.nElts)
+        self.ctx.check(self.ctx.lib.pa_tube_node_all(self.ctx.h, self.h, k.ptr, o.ptr))
+        return o.to_numpy(np.float64, (self.nElts,))
+
+    def node_avg(self, data, ncomp: int, comp: int) -> np.ndarray:
+        """pa_tube_node_avg -> [nElts]"""
+        d, o = _dev(self.ctx, data), self._out(self.nElts)
+        self.ctx.check(self.ctx.lib.pa_tube_node_avg(self.ctx.h, self.h, d.ptr, int(ncomp), int(comp), o.ptr))
+        return o.to_numpy(np.float64, (self.nElts,))
+
+    def smooth(self, vals, area, nSmooth: int) -> np.ndarray:
+        """pa_tube_smooth -> [nElts]"""
+        v, a, o = _dev(self.ctx, np.asarray(vals, np.float64)), _dev(self.ctx, np.asarray(area, np.float64)), self._out(self.nElts)
+        self.ctx.check(self.ctx.lib.pa_tube_smooth(self.ctx.h, self.h, v.ptr, a.ptr, int(nSmooth), o.ptr))
+        return o.to_numpy(np.float64, (self.nElts,))
+
+    def neighbors(self):
+        """pa_tube_neighbors -> (rowptr [nElts + 1] int64, cols [nnz] int32)"""
+        nnz = C.c_int64(0)
+        self.ctx.check(self.ctx.lib.pa_tube_neighbors(self.ctx.h, self.h, C.byref(nnz), None, None))
+        rp, cols = np.zeros(self.nElts + 1, np.int64), np.zeros(max(nnz.value, 1), np.int32)
+        self.ctx.check(self.ctx.lib.pa_tube_neighbors(self.ctx.h, self.h, C.byref(nnz), rp.ctypes.data_as(C.POINTER(C.c_int64)), cols.ctypes.data_as(C.POINTER(C.c_int32))))
+        return rp, cols[:nnz.value]
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.pa_tube_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.ctx.h:
+                self.close()
+        except Exception:
+            pass
 
 
 def iso_merge(ctx: Context, fragments, ncomp: int):

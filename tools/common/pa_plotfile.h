@@ -714,6 +714,25 @@ inline void write_mef(const std::string& file, double time, const std::vector<st
   f.write((const char*)e1.data(), sizeof(int32_t) * e1.size());
 }
 
+// the same file with a title line in place of the time (streamTubeStats.cpp:1610-1704: "Volume integrals", element-centred data on
+// multiply defined nodes)
+inline void write_mef(const std::string& file, const std::string& title, const std::vector<std::string>& names, const std::vector<double>& nodes /* [N][ncomp] */,
+                      const std::vector<int32_t>& elts0 /* [M][3], 0-based */) {
+  const int ncomp = (int)names.size();
+  const long long N = ncomp ? (long long)nodes.size() / ncomp : 0, M = (long long)elts0.size() / 3;
+  std::ofstream f(file, std::ios::binary);
+  if (!f) Abort("Unable to create " + file);
+  f << title << "\n";
+  for (int c = 0; c < ncomp; ++c) f << names[c] << (c + 1 < ncomp ? " " : "");
+  f << "\n" << M << " 3\n";
+  Box3 b{{0, 0, 0}, {(int)N - 1, 0, 0}};
+  f << "FAB ((8, (64 11 52 0 1 12 0 1023)),(8, (8 7 6 5 4 3 2 1)))" << box_str(b) << ' ' << ncomp << "\n";
+  f.write((const char*)nodes.data(), sizeof(double) * nodes.size());
+  std::vector<int32_t> e1(elts0.size());
+  for (size_t q = 0; q < elts0.size(); ++q) e1[q] = elts0[q] + 1;
+  f.write((const char*)e1.data(), sizeof(int32_t) * e1.size());
+}
+
 // reader of the same file, as the MEF consumers parse it (surfMEFtoDAT.cpp:46-72, checkIso.cpp:84-120)
 struct MefSurface {
   std::string title;
