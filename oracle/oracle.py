@@ -445,12 +445,18 @@ def smooth_apply(levels, x, dt, bc, MF):
 
 
 # ---------------------------------------------------------------- streamlines (partStream.cpp / StreamPC.cpp)
-def stream_field(levels, fields, comps, MF, ngrow=3):
+def stream_field(levels, fields, comps, MF, ngrow=3, ratio=None):
     """partStream.cpp:160-177: vector field with nGrow ghost layers, FillPatch with piecewise-constant
     interpolation from the coarser level, then FillBoundary.  Ghost cells outside a non-periodic domain
-    are left at 0.0 (the reference leaves them uninitialised)."""
+    are left at 0.0 (the reference leaves them uninitialised).  ratio: the refinement ratio between
+    consecutive levels (one int, or one per level pair); default: what the levels' domains say
+    (the plotfile's ratios[lev-1] of partStream.cpp:173-174)."""
     L = lib()
     out = []
+    if ratio is None:
+        ratio = [int(levels[l].domhi[0] - levels[l].domlo[0] + 1) // int(levels[l - 1].domhi[0] - levels[l - 1].domlo[0] + 1) for l in range(1, len(levels))]
+    elif np.ndim(ratio) == 0:
+        ratio = [int(ratio)] * (len(levels) - 1)
     for l, lv in enumerate(levels):
         v = MF(lv, 3, ngrow)
         for b in range(lv.nboxes):
@@ -458,21 +464,22 @@ def stream_field(levels, fields, comps, MF, ngrow=3):
                 v.valid(b)[d] = fields[l].valid(b)[c]
         fill_boundary(v, 0, 3, ngrow)
         if l > 0:
-            nbad = L.orc_fillpatch_two_levels(_p(_mf(v)), _p(_mf(out[l - 1])), 0, 3, ngrow, 2, 0)
-            assert nbad == 0
+            nbad = L.orc_fillpatch_two_levels(_p(_mf(v)), _p(_mf(out[l - 1])), 0, 3, ngrow, int(ratio[l - 1]), 0)
+            assert nbad == 0, f"level {l}: {nbad} coarse-fine ghost cells without coarse data (ratio {ratio[l - 1]})"
         out.append(v)
     return out
 
 
-def stream_trace(levels, vfield, seeds, nsteps, dt):
-    """orc_stream_trace -> (pos [2*nseed][nsteps][3], number of redistributions)"""
+def stream_trace(levels, vfield, seeds, nsteps, dt, vcomp=0):
+    """orc_stream_trace -> (pos [2*nseed][nsteps][3], number of redistributions); the vector is components
+    vcomp .. vcomp + 2 of vfield"""
     L = lib()
     seeds = np.ascontiguousarray(seeds, dtype=np.float64).reshape(-1, 3)
     pos = np.zeros((2 * len(seeds), nsteps, 3))
     va, keep = _mfptrs(vfield)
     nred = C.c_int32(0)
     L.orc_stream_trace.restype = C.c_int
-    rc = L.orc_stream_trace(len(levels), va, 0, C.c_int64(len(seeds)), seeds.ctypes.data_as(C.c_void_p), int(nsteps), C.c_double(dt),
+    rc = L.orc_stream_trace(len(levels), va, int(vcomp), C.c_int64(len(seeds)), seeds.ctypes.data_as(C.c_void_p), int(nsteps), C.c_double(dt),
                             pos.ctypes.data_as(C.c_void_p), C.byref(nred))
     if rc != 0:
         raise RuntimeError(f"bad RK (line {rc})")

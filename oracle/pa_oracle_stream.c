@@ -52,6 +52,9 @@ static int ntrpv(const double x[3], const orc_mf* v, int vcomp, int b, const tbx
   int bi[3];
   double n[3];
   const int ng = v->ng;
+  /* a position that is not finite (vnrml of an exactly zero vector is 0 * inf) is outside every FAB: decided here, not by
+   * the int conversion of NaN, which C leaves undefined (x86 gives INT_MIN, which is what makes the reference stop) */
+  if (!(isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]))) return 0;
   for (int d = 0; d < 3; ++d) {
     bi[d] = (int)floor((x[d] - plo[d]) / dx[d] - 0.5);
     n[d] = (x[d] - ((bi[d] + 0.5) * dx[d] + plo[d])) / dx[d];
@@ -113,7 +116,8 @@ static int rk4(double x[3], double dt, const orc_mf* v, int vcomp, int b, const 
 
 /* Where(): finest level whose grids contain the cell of x */
 static void where_is(int nlev, const orc_level* const* L, const double x[3], int* lev, int* grid) {
-  for (int l = nlev - 1; l >= 0; --l) {
+  const int finite = isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);  /* not finite: no grid, as in ntrpv */
+  for (int l = nlev - 1; finite && l >= 0; --l) {
     int p[3];
     for (int d = 0; d < 3; ++d) {
       const double dx = (L[l]->prob_hi[d] - L[l]->prob_lo[d]) / (double)(L[l]->domhi[d] - L[l]->domlo[d] + 1);

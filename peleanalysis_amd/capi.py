@@ -624,6 +624,8 @@ def stream_trace(ctx, vfield, vcomp, seeds, nsteps, dt):
     nred = C.c_int32(0)
     ctx.check(ctx.lib.pa_stream_trace(ctx.h, len(vfield), _handles(vfield), int(vcomp), n, seeds.ctypes.data_as(C.POINTER(C.c_double)), int(nsteps),
                                       float(dt), C.c_void_p(buf.ptr), C.byref(nred)))
+    if n == 0:  # nothing to copy back
+        return np.zeros((0, nsteps, 3)), nred.value
     return buf.to_numpy(np.float64, (2 * n, nsteps, 3)), nred.value
 
 

@@ -35,6 +35,9 @@ __device__ __forceinline__ bool s_ntrpv(const StreamLevels& S, int lev, int b, c
   int bi[3];
   double n[3];
   const int ng = S.ng;
+  // a position that is not finite (vnrml of an exactly zero vector is 0 * inf) is outside every FAB: decided here, not by
+  // the int conversion of NaN, which C++ leaves undefined and platforms answer differently
+  if (!(isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]))) return false;
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
     bi[d] = (int)floor((x[d] - S.plo[d]) / S.dx[lev][d] - 0.5);
@@ -96,7 +99,8 @@ __device__ __forceinline__ bool s_rk4(const StreamLevels& S, int lev, int b, con
 }
 
 __device__ __forceinline__ void s_where(const StreamLevels& S, const double x[3], int& lev, int& grid) {  // Redistribute -> Where()
-  for (int l = S.nlev - 1; l >= 0; --l) {
+  const bool finite = isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);  // not finite: no grid, as in s_ntrpv
+  for (int l = S.nlev - 1; finite && l >= 0; --l) {
     int p[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) p[d] = (int)floor((x[d] - S.plo[d]) / S.dx[l][d]);

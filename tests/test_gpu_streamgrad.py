@@ -11,6 +11,7 @@ import streamgrad_ref as R
 from peleanalysis_amd import capi
 from peleanalysis_amd.hierarchy import Hierarchy, Level, MultiFab, chop_box, field_flame, fill_analytic, nested_hierarchy, union_hierarchy
 from peleanalysis_amd.plotfile import read_mef, write_plotfile
+from stream_cases import ratio4_hierarchy as _ratio4_hierarchy
 from test_streamgrad_ref import CASES, golden_case
 
 pytestmark = pytest.mark.gpu
@@ -29,12 +30,6 @@ def test_vtrace_fab_reproduces_reference(ctx, name):
     if vc < 0:  # the materialised gradient of stream_nd.f90:33-44
         T = c["T"][0]
         assert np.array_equal(g[0], T[1:-1, 1:-1, 2:] - T[1:-1, 1:-1, :-2])
-
-
-def _ratio4_hierarchy(per):
-    l0 = Level(chop_box((0, 0, 0), (15, 15, 15), 8), (0, 0, 0), (15, 15, 15), per, np.zeros(3), np.ones(3))
-    l1 = Level(chop_box((16, 20, 16), (47, 43, 51), 16), (0, 0, 0), (63, 63, 63), per, np.zeros(3), np.ones(3))
-    return Hierarchy([l0, l1], 4)
 
 
 def _hier(kind, per):

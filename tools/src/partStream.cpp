@@ -59,7 +59,7 @@ int main(int argc, char** argv) {
   }
   std::string infile;
   pp.get("infile", infile);
-  pa::PlotfileHeader H = pa::read_header(infile);
+  pa::PlotfileHeader H = pa::read_header(infile, 3, /* any_ratio: partStream.cpp:34,173-174 take the file's */ true);
   const char* vnames[3] = {"x_velocity", "y_velocity", "z_velocity"};
   int vc[3];
   for (int d = 0; d < 3; ++d) {
@@ -94,8 +94,9 @@ int main(int argc, char** argv) {
               bool covered = false;
               if (lev + 1 < H.nlev)
                 for (const pa::Box3& F : H.lev[lev + 1].boxes) {
-                  // coarsen(F, 2) contains (i, j, k)?  (floor division: indices are non-negative inside the domain)
-                  auto cdiv = [](int a) { return a >= 0 ? a / 2 : -((-a + 1) / 2); };
+                  // coarsen(F, refRatio(lev)) contains (i, j, k)?  (partStream.cpp:34; floor division)
+                  const int rr = H.ref_ratio[(size_t)lev];
+                  auto cdiv = [rr](int a) { return a >= 0 ? a / rr : -((-a + rr - 1) / rr); };
                   if (i >= cdiv(F.lo[0]) && i <= cdiv(F.hi[0]) && j >= cdiv(F.lo[1]) && j <= cdiv(F.hi[1]) && k >= cdiv(F.lo[2]) && k <= cdiv(F.hi[2])) { covered = true; break; }
                 }
               if (covered) continue;
@@ -150,7 +151,7 @@ int main(int argc, char** argv) {
       dv.emplace_back(new pa::DevMF(ctx, *dl.back(), 3, nGrow));
       ctx.check(pa_mf_upload(ctx.h, dv.back()->h, hv[lev].data.data()));
       ctx.check(pa_fill_boundary(ctx.h, dv[lev]->h, 0, 3, nGrow));
-      if (lev > 0) ctx.check(pa_fillpatch_two_levels(ctx.h, dv[lev]->h, dv[lev - 1]->h, 0, 3, nGrow, 2, 0));  // PCInterp
+      if (lev > 0) ctx.check(pa_fillpatch_two_levels(ctx.h, dv[lev]->h, dv[lev - 1]->h, 0, 3, nGrow, H.ref_ratio[(size_t)lev - 1], 0));  // PCInterp, the file's ratio (partStream.cpp:173-174)
       v.push_back(dv[lev]->h);
     }
     ctx.check(pa_sync(ctx.h));
