@@ -551,6 +551,38 @@ int pa_condmean_add_level(pa_ctx*, pa_hist*, const pa_mf* comps, const pa_level*
 int pa_condmean_read(pa_ctx*, const pa_hist*, int64_t* hits, double* sum, double* sumsq, double* mn, double* mx);
 void pa_hist_destroy(pa_hist*);
 
+/* ------------------------------------------------------------- composite integrals (integral.cpp / rmsVel.cpp)
+ * One accumulator object (pa_integral) lives across the levels of a plotfile, as pa_hist does.  It projects the uncovered cells of
+ * every level onto a point (kind 3: volume integral), a line along `dir` (kind 2: plane integrals) or the plane normal to `dir`
+ * (kind 1: line integrals), at the resolution of the FINEST level that is integrated: 1, ldir or ldir1 x ldir2 slots, dir1 = (dir+1)%3
+ * the rows and dir2 = (dir+2)%3 the columns of the plane.  It holds nvars + 1 rows: row 0 the measure (volume, area, length), rows
+ * 1 .. nvars the sums of w * v_n and, with `squares`, rows nvars+1 .. 2 nvars the sums of (v_n * v_n) * w.  A cell of a level whose
+ * cells are R_l fine cells wide adds to the R_l (kind 2) or R_l x R_l (kind 1) fine slots under it.
+ * NUMERICS: the contract of the binned statistics above -- 192-bit fixed-point sums scaled from the magnitudes declared at begin,
+ * integer atomics, ONE rounding at read, the same bits for every run, tiling, box order and kernel variant; |S - sum t| <= 2^-53
+ * |sum t| (+ n quanta).  Row 0 is a cell count per level times the level's weight, summed exactly and rounded once.  A term that is
+ * not finite sets a sticky flag of its slot and row; read returns what IEEE addition gives in any order: NaN if a NaN or both
+ * infinities were seen, else the infinity that was seen, else the finite sum.  A finite term larger than twice the declared
+ * magnitude makes read fail.  One rank; 3-D levels.  add_level is asynchronous on the context's stream; begin and read are synchronous. */
+typedef struct pa_integral pa_integral;
+/* integral.cpp:442-449, :497-501, :520 (outdata) and rmsVel.cpp:82 (the seven sums): nvars <= 8, kind 1..3, dir 0..2 (unused by kind 3),
+ * domain = the index box of the finest level's problem domain (AmrData::ProbDomain()[finestLevel]) */
+pa_integral* pa_integral_create(pa_ctx*, int nvars, int kind, int dir, const pa_box* domain, int squares);
+/* zero + scales: w_max = the largest weight that will be added (level 0's), vabs[n] >= |value| of variable n */
+int pa_integral_begin(pa_ctx*, pa_integral*, double w_max, const double* vabs /* [nvars] */);
+/* integrate1d / 2d / 3d for one level (integral.cpp:24-44, :85-101, :129-140) and rmsVel.cpp:83-115: vars holds the nvars variables as
+ * components 0 .. nvars-1; a cell counts when its refined image has no owner on `finer` (integral.cpp:425-436; NULL: every cell) and,
+ * with ccomp >= 0, when cmin <= v_ccomp < cmax (a NaN fails).  R_l = the product of the refinement ratios from this level to the
+ * finest one: the level's domain times R_l must be the domain given at create.  w = dx*dy*dz (kind 3), dx[dir1]*dx[dir2] (kind 2) or
+ * dx[dir] (kind 1) of this level.  uncombined != 0: one set of global atomics per cell (measurement; identical bits). */
+int pa_integral_add_level(pa_ctx*, pa_integral*, const pa_mf* vars, const pa_level* finer, int ratio, int R_l, double w, int ccomp,
+                          double cmin, double cmax, int uncombined);
+/* the number of output slots per row */
+int64_t pa_integral_slots(const pa_integral*);
+/* the raw sums, before the avg division (integral.cpp:51-58, :107-112, :143-147; rmsVel.cpp:116-122): out[rows][slots] */
+int pa_integral_read(pa_ctx*, const pa_integral*, double* out);
+void pa_integral_destroy(pa_integral*);
+
 /* ------------------------------------------------------------- stream tubes (streamTubeStats.cpp)
  * The three lines through the nodes of a surface triangle bound a stream tube; between consecutive line points it is a wedge.
  * DATA LAYOUT: the Str FABs of a streamSampleFile, all levels and boxes back to back (box g after the boxes before it): a buffer of

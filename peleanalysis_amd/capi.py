@@ -200,6 +200,12 @@ def load_library() -> C.CDLL:
         "pa_condmean_add_level": (C.c_int, [vp, vp, vp, vp, C.c_int, C.POINTER(PaBox), i64, dbl, dbl, C.c_int]),
         "pa_condmean_read": (C.c_int, [vp, vp, C.POINTER(i64), pdbl, pdbl, pdbl, pdbl]),
         "pa_hist_destroy": (None, [vp]),
+        "pa_integral_create": (vp, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(PaBox), C.c_int]),
+        "pa_integral_begin": (C.c_int, [vp, vp, dbl, pdbl]),
+        "pa_integral_add_level": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, dbl, C.c_int, dbl, dbl, C.c_int]),
+        "pa_integral_slots": (i64, [vp]),
+        "pa_integral_read": (C.c_int, [vp, vp, pdbl]),
+        "pa_integral_destroy": (None, [vp]),
         "pa_tube_create": (vp, [vp, i32, C.POINTER(i64), i64, pi32, i64, pi32]),
         "pa_tube_destroy": (None, [vp]),
         "pa_tube_wedges": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
@@ -1044,3 +1050,49 @@ class CondMeanAcc(_Hist):
         self.ctx.check(self.ctx.lib.pa_condmean_read(self.ctx.h, self.h, hits.ctypes.data_as(C.POINTER(C.c_int64)), s.ctypes.data_as(pd), s2.ctypes.data_as(pd),
                                                      mn.ctypes.data_as(pd) if mn is not None else None, mx.ctypes.data_as(pd) if mx is not None else None))
         return hits, s, s2, mn, mx
+
+
+class IntegralAcc:
+    """the composite integrals of integral.cpp and the moments of rmsVel.cpp (pa_integral_*): rows = the measure, w * v of every
+    variable and, with squares, (v * v) * w of every variable; slots at the finest level's resolution"""
+
+    def __init__(self, ctx: Context, nvars: int, kind: int, dir: int, domain, squares: bool = False):
+        """domain: (lo0, lo1, lo2, hi0, hi1, hi2), the index box of the finest integrated level's problem domain"""
+        self.ctx, self.nvars, self.kind, self.dir, self.squares = ctx, int(nvars), int(kind), int(dir), bool(squares)
+        bx = PaBox()
+        for d in range(3):
+            bx.lo[d], bx.hi[d] = int(domain[d]), int(domain[3 + d])
+        self.h = ctx.lib.pa_integral_create(ctx.h, int(nvars), int(kind), int(dir), C.byref(bx), int(bool(squares)))
+        if not self.h:
+            raise PaError(ctx.lib.pa_last_error(ctx.h).decode())
+        self.nrows = 1 + self.nvars * (2 if self.squares else 1)
+        n = [int(domain[3 + d]) - int(domain[d]) + 1 for d in range(3)]
+        self.shape = () if self.kind == 3 else ((n[self.dir],) if self.kind == 2 else (n[(self.dir + 1) % 3], n[(self.dir + 2) % 3]))
+        assert int(np.prod(self.shape, dtype=np.int64)) == ctx.lib.pa_integral_slots(self.h)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.pa_integral_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def begin(self, w_max: float, vabs):
+        a = np.ascontiguousarray(vabs, dtype=np.float64)
+        assert len(a) == self.nvars
+        self.ctx.check(self.ctx.lib.pa_integral_begin(self.ctx.h, self.h, float(w_max), a.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def add_level(self, mf: "DevMF", finer: Optional["DevLevel"], ratio: int, R: int, w: float, ccomp: int = -1, cmin: float = 0.0, cmax: float = 0.0,
+                  uncombined: bool = False):
+        self.ctx.check(self.ctx.lib.pa_integral_add_level(self.ctx.h, self.h, mf.h, finer.h if finer is not None else None, int(ratio), int(R), float(w),
+                                                          int(ccomp), float(cmin), float(cmax), int(bool(uncombined))))
+
+    def read(self):
+        """raw sums -> array [rows] + shape (kind 3: [rows]; kind 2: [rows][ldir]; kind 1: [rows][ldir1][ldir2])"""
+        out = np.zeros((self.nrows,) + self.shape)
+        self.ctx.check(self.ctx.lib.pa_integral_read(self.ctx.h, self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
