@@ -190,7 +190,53 @@ __global__ __launch_bounds__(64 * TY) void k_smooth_march(SmArgs A) {
   }
 }
 
-// reflux from the fine side: thread per coarse face of a special fine face (coarse-fine cells only)
+// Reflux from the fine side.  Face o = 2 * dir + side of the UNCOVERED coarse cell ow (wrapped into the domain) is coarse-fine when
+// the coarse cell behind it -- on the low side of ow for side = 1, as in k_smooth_reflux_apply -- lies under a fine box: that box, and
+// the cell nb behind the face (wrapped), or -1
+__device__ __forceinline__ int reflux_face(const DLevelView& LF, const DLevelView& LC, const int ow[3], int o, int ratio, int nb[3]) {
+  const int dir = o >> 1, side = o & 1;
+  nb[0] = ow[0]; nb[1] = ow[1]; nb[2] = ow[2];
+  nb[dir] += side ? -1 : 1;
+  if (!wrap_cell(LC, nb)) return -1;
+  const int f[3] = {nb[0] * ratio, nb[1] * ratio, nb[2] * rdir(LF, 2, ratio)};
+  return owner_of(LF, f);
+}
+// the correction of y(ow) through that face: dt / dx_c * (average fine flux - the coarse flux the 7-point apply used), signed
+__device__ __forceinline__ bool reflux_corr(const DLevelView& LF, const DMFView& XF, const DLevelView& LC, const DMFView& XC, const int ow[3], double xo, int o,
+                                            double dt, int ratio, double& corr) {
+  int nb[3];
+  const int fb = reflux_face(LF, LC, ow, o, ratio, nb);
+  if (fb < 0) return false;
+  const int ib = owner_of(LC, nb);
+  if (ib < 0) return false;
+  const int dir = o >> 1, side = o & 1;
+  const DBox B = LF.boxes[fb];
+  const int t0 = (dir == 0) ? 1 : 0, t1 = (dir == 2) ? 1 : 2;
+  const int r0 = rdir(LF, t0, ratio), r1 = rdir(LF, t1, ratio);
+  const int gq = side ? B.hi[dir] + 1 : B.lo[dir] - 1, inq = side ? B.hi[dir] : B.lo[dir];  // (ow is uncovered: the face is a face of the box)
+  const double* xf = XF.data + XF.off[fb];
+  const double dxf = LF.dxinv[dir], dxc = LC.dxinv[dir];
+  double favg = 0.0;
+  for (int v = 0; v < r1; ++v)
+    for (int uu = 0; uu < r0; ++uu) {
+      int g[3], in[3];
+      g[dir] = gq; in[dir] = inq;
+      g[t0] = in[t0] = nb[t0] * r0 + uu;
+      g[t1] = in[t1] = nb[t1] * r1 + v;
+      const double xg = xf[fab_index(B, XF.ng, XF.ncomp, 0, g[0], g[1], g[2])], xi = xf[fab_index(B, XF.ng, XF.ncomp, 0, in[0], in[1], in[2])];
+      favg += side ? dxf * (xg - xi) : dxf * (xi - xg);
+    }
+  favg *= 1.0 / (double)(r0 * r1);
+  const double xin = XC.data[XC.off[ib] + fab_index(LC.boxes[ib], XC.ng, XC.ncomp, 0, nb[0], nb[1], nb[2])];
+  const double fc = side ? dxc * (xo - xin) : dxc * (xin - xo);
+  corr = dt * (dxc * (favg - fc));
+  if (!side) corr = -corr;
+  return true;
+}
+// Thread per coarse face of a special fine face (coarse-fine cells only).  A coarse cell in a CONCAVE corner of the fine region takes
+// corrections through two or three of its faces: the thread of its lowest coarse-fine face adds them all, in face order 0..5 (the
+// order of k_smooth_reflux_apply), the others leave -- one writer per coarse cell, no atomics, a fixed summation order.  A cell
+// with one coarse-fine face gets y + corr as before.
 __global__ __launch_bounds__(256) void k_smooth_reflux(DLevelView LF, DMFView XF, DLevelView LC, DMFView XC, DMFView YC, double dt, int ratio) {
   const int e = LF.sfaces[blockIdx.y];
   const int b = e / 6, dir = (e % 6) >> 1, side = e & 1;
@@ -205,33 +251,23 @@ __global__ __launch_bounds__(256) void k_smooth_reflux(DLevelView LF, DMFView XF
   const int a0 = (int)(u - r * c0), b1 = (int)r;  // coarse offsets inside the face
   // class of the first child ghost cell: 1 = coarse-fine (a coarse cell is covered entirely or not at all)
   if ((LF.sfcode[LF.sfoff[blockIdx.y] + (long long)(a0 * r0) + (long long)n0 * (b1 * r1)] & 3u) != 1u) return;
-  const int gq = side ? B.hi[dir] + 1 : B.lo[dir] - 1, inq = side ? B.hi[dir] : B.lo[dir];
-  int oc[3], ic[3];
-  oc[dir] = coarsen_idx(gq, rn); ic[dir] = coarsen_idx(inq, rn);
-  oc[t0] = ic[t0] = coarsen_idx(B.lo[t0], r0) + a0;
-  oc[t1] = ic[t1] = coarsen_idx(B.lo[t1], r1) + b1;
-  int ow[3] = {oc[0], oc[1], oc[2]}, iw[3] = {ic[0], ic[1], ic[2]};
-  if (!wrap_cell(LC, ow) || !wrap_cell(LC, iw)) return;
-  const int ob = owner_of(LC, ow), ib = owner_of(LC, iw);
-  if (ob < 0 || ib < 0) return;
-  const double* xf = XF.data + XF.off[b];
-  const double dxf = LF.dxinv[dir], dxc = LC.dxinv[dir];
-  double favg = 0.0;
-  for (int v = 0; v < r1; ++v)
-    for (int uu = 0; uu < r0; ++uu) {
-      int g[3], in[3];
-      g[dir] = gq; in[dir] = inq;
-      g[t0] = in[t0] = B.lo[t0] + a0 * r0 + uu;
-      g[t1] = in[t1] = B.lo[t1] + b1 * r1 + v;
-      const double xg = xf[fab_index(B, XF.ng, XF.ncomp, 0, g[0], g[1], g[2])], xi = xf[fab_index(B, XF.ng, XF.ncomp, 0, in[0], in[1], in[2])];
-      favg += side ? dxf * (xg - xi) : dxf * (xi - xg);
-    }
-  favg *= 1.0 / (double)(r0 * r1);
+  int ow[3];
+  ow[dir] = coarsen_idx(side ? B.hi[dir] + 1 : B.lo[dir] - 1, rn);
+  ow[t0] = coarsen_idx(B.lo[t0], r0) + a0;
+  ow[t1] = coarsen_idx(B.lo[t1], r1) + b1;
+  if (!wrap_cell(LC, ow)) return;
+  const int ob = owner_of(LC, ow);
+  if (ob < 0) return;
+  const int mine = 2 * dir + side;
+  int nb[3];
+  for (int o = 0; o < mine; ++o)
+    if (reflux_face(LF, LC, ow, o, ratio, nb) >= 0) return;  // the thread of that face does this cell
   const double xo = XC.data[XC.off[ob] + fab_index(LC.boxes[ob], XC.ng, XC.ncomp, 0, ow[0], ow[1], ow[2])];
-  const double xin = XC.data[XC.off[ib] + fab_index(LC.boxes[ib], XC.ng, XC.ncomp, 0, iw[0], iw[1], iw[2])];
-  const double fc = side ? dxc * (xo - xin) : dxc * (xin - xo);
-  const double corr = dt * (dxc * (favg - fc));
-  atomicAdd(&YC.data[YC.off[ob] + fab_index(LC.boxes[ob], YC.ng, YC.ncomp, 0, ow[0], ow[1], ow[2])], side ? corr : -corr);
+  double* yp = &YC.data[YC.off[ob] + fab_index(LC.boxes[ob], YC.ng, YC.ncomp, 0, ow[0], ow[1], ow[2])];
+  double y = *yp, corr;
+  for (int o = mine; o < 6; ++o)
+    if (reflux_corr(LF, XF, LC, XC, ow, xo, o, dt, ratio, corr)) y += corr;
+  *yp = y;
 }
 
 __global__ __launch_bounds__(256) void k_smooth_zero_covered(DLevelView L, DMFView Y, DMFView M) {
@@ -970,7 +1006,7 @@ struct SmoothSolver {
 
 // A hierarchy sharded over ranks, REPLICATED form (PA_SMOOTH_REPLICATED=1): every rank gathers the right-hand side of the whole
 // hierarchy (one grouped exchange, RepPlan in pa_dist.hip), runs the same composite solve on its own GPU -- same input, same
-// kernels, same fixed summation order, so every rank gets the same field and the result equals the one-rank run BIT FOR BIT --
+// kernels, same fixed summation order (the reflux of a concave corner included), so every rank gets the same field and the result equals the one-rank run BIT FOR BIT --
 // and keeps the boxes it owns.  No speed-up with the number of GPUs and (nranks - 1) x this rank's cells of send buffer: the
 // default is the distributed solve below (the reference's MLMG distributes this solve too); this form stays for runs that
 // must reproduce the one-GPU bits.

@@ -220,6 +220,9 @@ def _smooth_worker(rank, world, port, case, transport="gloo"):
         elif case.startswith("walls"):
             per = (0, 0, 0)
             H = nested_hierarchy(16, 3, 8, is_per=per)
+        elif case.startswith("hand"):  # L-shaped levels with concave coarse-fine corners: coarse cells refluxed through two or three faces
+            import smooth_cases
+            H = smooth_cases.hand(per)
         elif case.startswith("2d"):  # the AMREX_SPACEDIM == 2 build: one plane of cells per level, refined in x and y only
             from peleanalysis_amd.hierarchy import Hierarchy, Level, chop_box
             per = (1, 0, 0)
@@ -287,19 +290,31 @@ def _smooth_worker(rank, world, port, case, transport="gloo"):
             for i, g in enumerate(dl.gids):
                 worst = max(worst, float(np.abs(got.valid(i)[0] - want[l].valid(int(g))[0]).max()))
         assert worst <= (1e-10 if stiff else 1e-12), f"rank {rank}/{world}: smoothed field differs from the undistributed oracle by {worst}"
+        if replicated:  # same input, same kernels, fixed summation order (the reflux of a concave corner included): the ONE-RANK solve's bits
+            ols = [capi.DevLevel(ctx, lv) for lv in H.levels]
+            orhs = [capi.DevMF.from_host(ctx, dl, r) for dl, r in zip(ols, rhs)]
+            osol = [capi.DevMF(ctx, dl, 1, 0) for dl in ols]
+            it1, res1 = capi.smooth_solve(ctx, orhs, 0, osol, 0, dt, bc, tol=1e-13 if stiff else 1e-14, maxiter=200)
+            assert (it1, res1) == (it, res), ((it1, res1), (it, res))
+            one = [m.download() for m in osol]
+            for l, dl in enumerate(dls):
+                got = dsol[l].download()
+                for i, g in enumerate(dl.gids):
+                    assert np.array_equal(got.valid(i)[0], one[l].valid(int(g))[0]), f"rank {rank}/{world}: replicated solve != one-rank solve, level {l} box {int(g)}"
         dist.barrier()
         ctx.close()
     finally:
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,case", [(2, "nested"), (4, "nested"), (3, "walls"), (4, "nested+rep"), (3, "randu0"), (4, "randu13"), (2, "randu2"), (3, "randU0"), (4, "rand7"), (3, "2d"),
+@pytest.mark.parametrize("world,case", [(2, "nested"), (4, "nested"), (3, "walls"), (4, "nested+rep"), (2, "hand+rep"), (3, "randu0"), (4, "randu13"), (2, "randu2"), (3, "randU0"), (4, "rand7"), (3, "2d"),
                                         (2, "nested+mg"), (4, "nested+mg"), (3, "walls+mg"), (3, "2d+mg")])
 def test_sharded_smoothing_solve_matches_undistributed_oracle(world, case):
     """do_smooth with the hierarchy dealt to `world` ranks (scattered owners: fine boxes, their coarse parents and their
     neighbours mostly on different ranks): average_down and the flux register through the restriction plans, dot products
     through the transport's allreduce; the field equals the oracle's one-process composite solve to 1e-12 (both iterated to
-    1e-14), with the one-rank iteration count.  `+rep`: the replicated form (PA_SMOOTH_REPLICATED=1)."""
+    1e-14), with the one-rank iteration count.  `+rep`: the replicated form (PA_SMOOTH_REPLICATED=1), which also
+    equals the one-rank solve bit for bit -- on `hand` with coarse cells that take reflux corrections through several faces."""
     import torch.multiprocessing as mp
     mp.spawn(_smooth_worker, args=(world, _free_port(), case), nprocs=world, join=True)
 
