@@ -575,7 +575,7 @@ pa_level* pa_level_create_spec(pa_ctx* ctx, const LevelSpec& S, const int32_t do
     for (int d = 0; d < 3; ++d)
       for (int side = 0; side < 2; ++side)
         if (pa_face_is_special(L, L->boxes[b], d, side)) L->sfaces.push_back(b * 6 + d * 2 + side);
-  // Pure special faces (the exact-normal sweep of pa_fused2.hip wants them): a face with a ghost cell that is not a valid
+  // Pure special faces (the exact-normal sweep of pa_fused_sweep.hip wants them): a face with a ghost cell that is not a valid
   // cell has NO ghost cell that is one.  Again a property of the whole BoxArray (all ranks take the same path).
   L->pure_faces = true;
   for (int b = 0; b < nfus && L->pure_faces; ++b) {
@@ -1045,8 +1045,6 @@ __global__ __launch_bounds__(256) void k_fill_boundary_regions(LevBatch<FbrArgs>
   for (int c = 0; c < Fa.ncomp; ++c) dst[c * csd] = src[c * css];
 }
 
-int pa_fill_boundary_local_batch(pa_ctx* ctx, int n, pa_mf* const* Ms, int comp, int ncomp, int ng);
-int pa_fill_boundary_local_batch_ngs(pa_ctx* ctx, int n, pa_mf* const* Ms, int comp, int ncomp, const int* ngs);
 static long long max_shell(const pa_level* L, int ng) {
   long long m = 0;
   for (const DBox& B : L->boxes) {

@@ -198,7 +198,7 @@ static void plan_fill_boundary(const std::vector<DBox>& boxes, const std::vector
 
 struct CsPiece { int cbox; DBox box; };
 
-// Can box B have IRREGULAR cells (pa_fused.hip: k_find_irregular)?  A test at the granularity of the owner grid, true for every
+// Can box B have IRREGULAR cells (pa_fused_irreg.hip: k_find_irregular)?  A test at the granularity of the owner grid, true for every
 // box with such a cell (and for a few without): a face that is partly covered by a neighbouring box and partly not, or an
 // edge ghost line that is a concave corner of the level (not a valid cell while both its face-ring neighbours are) or a
 // valid cell next to a special face.  Pure geometry of the whole BoxArray: every rank gives the same answer for every box.

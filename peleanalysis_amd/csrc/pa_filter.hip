@@ -1015,7 +1015,6 @@ extern "C" int pa_fillpatch_two_levels(pa_ctx* ctx, pa_mf* fine, const pa_mf* cr
   return 0;
 }
 
-int pa_fill_boundary_local_batch_ngs(pa_ctx* ctx, int n, pa_mf* const* Ms, int comp, int ncomp, const int* ngs);
 // The ghost fill of a whole hierarchy -- filterPlt.cpp:159-203 (FillBoundary, FillPatchTwoLevels, foextrap per level) and
 // isosurface.cpp:1468-1524 (FillBoundary + FillPatchTwoLevels with PCInterp) -- in THREE launches instead of three per level:
 // FillBoundary of every level, FillPatchTwoLevels of every level pair, foextrap of every level.  Legal because no step of a

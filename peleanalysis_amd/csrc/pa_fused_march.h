@@ -23,7 +23,7 @@
 // Ghost cells of phi that are NOT valid cells of the level (coarse-fine / physical walls) give a
 // c that differs from the reference's (which applies the boundary condition to c itself); every
 // result that depends on such a cell lies within two cells of a coarse-fine or wall face and is
-// recomputed by k_gradcurv_faces (pa_fused.hip).  Everywhere else results are bit-identical to
+// recomputed by the fix-up (pa_fused_fix.hip).  Everywhere else results are bit-identical to
 // the pass-by-pass path and to the CPU oracle (same operation order: cdiff, normal_from).
 #pragma once
 #include "pa_fabview.h"

@@ -112,9 +112,9 @@ __device__ __forceinline__ void store_pair(char* base, unsigned off, bool odd, d
 
 // CG: the progress variable in the ghost cells behind SPECIAL box faces (coarse-fine / wall) is not (phi_ghost - pmin) *
 // invdenom but the reference's boundary condition applied to c itself; with CG the kernel takes those values from the
-// level's compact face-major arrays (DLevelView::cg, filled by k_prep_faces in pa_fused2.hip), so the flame normal is
+// level's compact face-major arrays (DLevelView::cg, filled by k_prep_faces_chunks in pa_fused_prep.hip), so the flame normal is
 // exact in EVERY valid cell and the curvature everywhere except in the first layer behind such a face (whose ghost
-// normal comes from the boundary condition on n: pa_fused2.hip).  Where the arrays are read:
+// normal comes from the boundary condition on n: pa_fused_fix.hip).  Where the arrays are read:
 //   z faces  output rows: c of plane lo_z - 1 (prologue) / hi_z + 1 (one select per step);
 //   y faces  the halo row wave IS the ghost row: its second stream (the row beyond, only needed for the ghost normal,
 //            which is irrelevant there) is re-aimed at the array, one plane ahead;

@@ -53,12 +53,12 @@ struct DLevelView {
   const int* sfindex;           // [nboxes*6] entry of a box face in sfaces, or -1 (ordinary face: every ghost cell is a valid cell)
   const long long* sfoff;       // [nsf] start of the face's ghost-cell codes in sfcode
   const unsigned short* sfcode; // cf_masks of every ghost cell of every special face, (t0 fastest, t1) per face
-  // Resolved ghost values of the progress variable behind every special face, compact and FACE-MAJOR (pa_fused2.hip):
+  // Resolved ghost values of the progress variable behind every special face, compact and FACE-MAJOR (pa_fused_prep.hip):
   // face e holds (n0+2) x (n1+2) doubles at cg + cgoff[e], element (a0, a1) = a1 * (n0+2) + a0 with a0 / a1 = tangential
   // coordinate - box lo + 1 (a ring of one cell for the edge ghosts), + 2 rows of slack.  Null: not allocated.
   const long long* cgoff;
   double* cg;
-  // Coarse patches (pa_fused.hip, k_cpatch): for every special coarse-fine face the coarse values its boundary
+  // Coarse patches (pa_fused_prep.hip, k_cpatch): for every special coarse-fine face the coarse values its boundary
   // interpolation can touch -- the coarse plane behind the face, tangentially coarsen(lo - 1) - 2 .. coarsen(hi + 1) + 2 --
   // as one dense 2-D array at cp + cpoff[e] (cpoff < 0: a wall face).  Filled by a gather pass so that the face kernels
   // read coarse data without owner-map lookups.  Null: not allocated.
@@ -66,7 +66,7 @@ struct DLevelView {
   double* cp;
 };
 
-// One work item of the chunked special-face kernels (round 6, pa_fused.hip: k_prep_faces_chunks / k_faces_fix_chunks): a rectangle
+// One work item of the chunked special-face kernels (round 6, pa_fused_prep.hip: k_prep_faces_chunks, pa_fused_fix.hip: k_faces_fix_chunks): a rectangle
 // (u0 .. u0 + cw - 1) x (v0 .. v0 + ch - 1) of the ghost cells of ONE special face in the face's tangential coordinates (t0 fastest),
 // cw * ch = 1024, one thread per 2 x 2 block; blocks start on even GLOBAL indices (the four ghost cells of a block share one coarse
 // parent), so u0 / v0 are -1 where the face starts on an odd index: cells outside the face are predicated off.  Everything the kernels need to know about the face sits in the record -- one wide
@@ -104,7 +104,7 @@ struct DMFView {
 // level and kernel costs more than the work): blockIdx.y runs over the concatenated rows (boxes / special faces) of up to
 // PA_MAXB levels; level l owns rows ycum[l] .. ycum[l+1]-1.  Passed by value (kernel arguments, < 4 KB).
 #define PA_MAXB 4
-#define PA_MAXSLOTS 16  // component slots per batch of the boundary kernels (pa_fused.hip: SlotK)
+#define PA_MAXSLOTS 16  // component slots per batch of the boundary kernels (pa_fused.h: SlotK)
 template <typename A, int CAP = PA_MAXB>
 struct LevBatch {
   int n = 0;
@@ -126,8 +126,8 @@ struct pa_ctx {
   double* d_red = nullptr;  // reduction scratch
   size_t red_cap = 0;
   int* d_flags = nullptr;   // [0] = coarse-fine ghost cells whose coarse data was missing
-  void* d_slow = nullptr;   // cells the clip-aware curvature fix-up hands to its general path (pa_fused.hip: SlowList)
-  hipEvent_t fix_evs[2] = {nullptr, nullptr};  // fix-up: perimeter kernel on the side stream (pa_fused.hip)
+  void* d_slow = nullptr;   // cells the clip-aware curvature fix-up hands to its general path (pa_fused_fix.hip: SlowList)
+  hipEvent_t fix_evs[2] = {nullptr, nullptr};  // fix-up: perimeter kernel on the side stream (pa_fused_fix.hip)
   double* d_prog = nullptr; // (pmin, 1 / (pmax - pmin)) of the component slots of a batch (pa_gradcurv_run_comps2)
   void* d_scr = nullptr;    // grow-only scratch (marching cubes)
   size_t scr_cap = 0;
@@ -179,7 +179,7 @@ struct ProfScope {
 enum { PA_TAG_GRADCURV = 1, PA_TAG_GRADCURV_FACES = 2, PA_TAG_FILL = 3, PA_TAG_BC = 4, PA_TAG_GRAD = 5, PA_TAG_PROGRESS = 6,
        PA_TAG_FILTER = 7, PA_TAG_MC = 8, PA_TAG_XCHG = 9 };
 
-// Workgroup table of a sweep over boxes of DIFFERENT sizes (pa_fused.hip: sweep_wgtab): entry i = {box, tile of that box} or
+// Workgroup table of a sweep over boxes of DIFFERENT sizes (pa_fused_sweep.hip: sweep_wgtab): entry i = {box, tile of that box} or
 // {-1, 0}; groups of 8 boxes with similar tile counts are interleaved so that entry i and i + 8 (same XCD) belong to one box
 struct WgTab {
   int* d = nullptr;
@@ -211,10 +211,10 @@ struct pa_level {
   int maxn[3] = {0, 0, 0};  // max box extent per dim
   long long ncells = 0;
   bool fusable = true;      // no concave coarse-fine corner (see pa_level_create)
-  bool pure_faces = true;   // every special face of the WHOLE BoxArray has no ghost cell that is a valid cell (pa_fused2.hip)
+  bool pure_faces = true;   // every special face of the WHOLE BoxArray has no ghost cell that is a valid cell (pa_fused_prep.hip)
   long long* d_cpoff = nullptr;
   double* d_cp = nullptr;   // allocated on first use (level_cp)
-  int cp_sets = 0, cg_sets = 0;  // component slots the buffers hold (pa_fused.hip: SlotK)
+  int cp_sets = 0, cg_sets = 0;  // component slots the buffers hold (pa_fused.h: SlotK)
   long long cp_total = 0;
   long long* d_cgoff = nullptr;
   double* d_cg = nullptr;   // allocated on first use (pa_level_cg)
@@ -223,10 +223,10 @@ struct pa_level {
   bool ncg_live = false;    // this pass's sweep wrote them (set by pa_gradcurv_levels_cg, consumed by pa_gradcurv_fix_levels)
   int ncg_minw = 0;         // ... for the boxes at least this wide
   std::vector<long long> cgoff;
-  // Irregular cells (pa_fused.hip: k_find_irregular / k_curv_general): boundary cells of local boxes next to a concave
+  // Irregular cells (pa_fused_irreg.hip: k_find_irregular, pa_fused_fix.hip: k_curv_general): boundary cells of local boxes next to a concave
   // coarse-fine corner or to the line where a box face changes from covered to coarse-fine, whose curvature neither the
   // sweep nor the face fix-up gets right; recomputed one by one through a geometry-independent path.  Built on first use.
-  // Sweep groups (pa_fused.hip): boxes wider than 32 cells take the wide sweep kernel (64-column tiles), the others the narrow
+  // Sweep groups (pa_fused_sweep.hip): boxes wider than 32 cells take the wide sweep kernel (64-column tiles), the others the narrow
   // one (two 32-column rows per wavefront); a level that has both kinds keeps two index lists (wide first) for the two launches
   int* d_blist = nullptr;
   int nwide = 0, nnarrow = 0;
@@ -239,7 +239,7 @@ struct pa_level {
   int npfwg = 0;
   SfChunk* d_sfchunk = nullptr;  // the chunk records of the level's special faces (round 6)
   int nsfchunk = 0;
-  void* d_ring = nullptr;   // RingItem (pa_fused.hip): the edge ghost cells whose resolved progress variable goes into a face's ring, built on first use
+  void* d_ring = nullptr;   // RingItem (pa_fused_prep.hip): the edge ghost cells whose resolved progress variable goes into a face's ring, built on first use
   int nring = -1;           // -1: not built yet
   std::vector<unsigned char> xneed;  // per box: bits 1 / 2 as pa_sweep_gneed (built on first use)
   void* d_irr = nullptr;    // int4 {box, i, j, k}
@@ -260,7 +260,7 @@ struct pa_level {
   mutable std::map<int, std::unique_ptr<struct FbLocal>> fb_local;                     // local FillBoundary as copy regions, by ghost width (pa_dist.hip)
   mutable std::map<std::pair<long long, int>, std::unique_ptr<struct CsPlan>> cs_plans; // coarse-source plans by (coarse level serial, mode)
   mutable std::unique_ptr<struct RepPlan> rep_plan;                                     // the level replicated on every rank (pa_dist.hip)
-  mutable std::map<long long, std::unique_ptr<WgTab>> wgtabs;                           // sweep workgroup tables by (group, tile shape) (pa_fused.hip)
+  mutable std::map<long long, std::unique_ptr<WgTab>> wgtabs;                           // sweep workgroup tables by (group, tile shape) (pa_fused_sweep.hip)
   mutable std::map<long long, std::unique_ptr<struct RsPlan>> rs_plans;                 // restriction onto a sharded coarse level, by coarse level serial (pa_dist.hip)
   mutable std::map<std::pair<long long, int>, std::unique_ptr<struct FpPlan>> fp_plans; // FillPatchTwoLevels parent lists by (coarse level serial, ghost width) (pa_filter.hip)
   mutable std::map<std::array<int, 3>, struct pa_mf*> scratch;                          // work multifabs by (components, ghost width, role), kept for the level's lifetime (pa_level_scratch)
@@ -317,6 +317,45 @@ struct pa_mf {
   } while (0)
 
 int pa_fail(pa_ctx* ctx, const std::string& msg);
+
+// ---- functions defined in one .hip and called from another (not part of the C ABI).  The file that defines one includes this
+// header, so the compiler compares declaration and definition; default arguments live here only.
+// pa_core.hip
+int pa_ensure_red(pa_ctx* ctx, size_t n);
+int pa_fill_boundary_impl(pa_ctx* ctx, pa_mf* M, int comp, int ncomp, int ng, int no_exchange);
+int pa_fill_boundary_local_batch(pa_ctx* ctx, int n, pa_mf* const* Ms, int comp, int ncomp, int ng);
+int pa_fill_boundary_local_batch_ngs(pa_ctx* ctx, int n, pa_mf* const* Ms, int comp, int ncomp, const int* ngs);
+int pa_apply_bc_impl(pa_ctx* ctx, pa_mf* F, int comp, const pa_mf* C, int ccomp, const int32_t bc[3], int ratio, int only_dir,
+                     int edges, const double* crse_xform);
+int pa_apply_bc_dual(pa_ctx* ctx, pa_mf* F0, int comp0, pa_mf* F1, int comp1, const pa_mf* C, int ccomp, const int32_t bc[3], int ratio,
+                     const double* xform);
+// pa_stencil.hip
+int pa_grad_levels(pa_ctx* ctx, int nlev, pa_mf* const* phi, int comp, pa_mf* const* out, int ocomp);
+// pa_curvopts.hip
+int pa_gauss_curv_level(pa_ctx* ctx, const pa_mf* G, int gcomp, const pa_mf* normgrad, int ngcomp, const pa_mf* c, int ccomp, double thr, pa_mf* out,
+                        int kcomp);
+int pa_strain_level(pa_ctx* ctx, const pa_mf* u, int ucomp, pa_mf* out, int srcomp, int rostcomp);
+int pa_velnormal_level(pa_ctx* ctx, const pa_mf* u, int ucomp, const pa_mf* n, int ncomp0, const pa_mf* c, int ccomp, double thr, pa_mf* out, int ocomp);
+int pa_curvopts_level(pa_ctx* ctx, int which, const pa_mf* G, const pa_mf* u, int ucomp, pa_mf* out, int pc, int nc, int kgc, int src, int vnc, int rostc, double thr);
+// the fused grad -> curvature path as the level loops (pa_pipeline.hip) see it; what its units share among themselves: pa_fused.h
+// pa_fused_prep.hip
+int pa_gradcurv_prep_levels(pa_ctx* ctx, int nlev, pa_mf* const* phi, int comp, const pa_mf* const* crse, int ccomp, const int32_t bc[3], double pmin, double pmax, int phase = 3,
+                            int nslots = 1, const double* prog = nullptr);
+// pa_fused_sweep.hip
+bool pa_gradcurv_gout_ok(int nlev, pa_mf* const* phi);
+bool pa_gradcurv_parts_ok(int nlev, pa_mf* const* phi);
+bool pa_gradcurv_kg_ok(int nlev, pa_mf* const* phi);
+int pa_gradcurv_levels_cg(pa_ctx* ctx, int nlev, pa_mf* const* phi, int pcomp, double pmin, double pmax, pa_mf* const* out, int ocomp, double thr = -1.0, int slot = 0,
+                          int nslots = 1, const double* prog = nullptr, const double* pmins = nullptr, const double* pmaxs = nullptr, pa_mf* const* gout = nullptr, int part = 0, int kg = 0);
+// pa_fused_fix.hip
+int pa_gradcurv_faces_phase(pa_ctx* ctx, const pa_mf* c, int ccomp, const pa_mf* crse_n, int cncomp0, const int32_t bc[3], int ratio, double thr,
+                            pa_mf* out, int ncomp0, int kcomp, int phase);
+int pa_gradcurv_fix_levels(pa_ctx* ctx, int nlev, pa_mf* const* phi, int pcomp, const pa_mf* const* crse_n, int cncomp0, const int32_t bc[3], double pmin, double pmax,
+                           pa_mf* const* out, int ncomp0, int kcomp, double thr = -1.0, int nslots = 1, const double* prog = nullptr, int cn_z = 8,
+                           const pa_mf* const* crse_phi = nullptr, int cpcomp = 0);
+// pa_fused_irreg.hip
+bool pa_fused2_level_ok(const pa_level* L);
+int pa_gauss_cells_levels(pa_ctx* ctx, int nlev, pa_mf* const* G, pa_mf* const* out, int pc, int kgc, double thr);
 
 // The current HIP device is per host thread, and a pa_ctx may be used from a thread other than the one that created it
 // (tools bring the context up on a worker thread) or next to contexts of other devices (ngpus > 1 in one process):

@@ -20,10 +20,6 @@
 #include <memory>
 #include <vector>
 
-int pa_ensure_red(pa_ctx* ctx, size_t n);
-int pa_fill_boundary_impl(pa_ctx* ctx, pa_mf* M, int comp, int ncomp, int ng, int no_exchange);
-int pa_apply_bc_impl(pa_ctx* ctx, pa_mf* F, int comp, const pa_mf* C, int ccomp, const int32_t bc[3], int ratio, int only_dir, int edges, const double* crse_xform);
-
 struct BoxIt {  // thread -> cell of box blockIdx.y (grid-stride over the box's valid cells)
   DBox B;
   int nx, ny, nz;

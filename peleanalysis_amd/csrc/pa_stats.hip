@@ -127,8 +127,6 @@ __global__ __launch_bounds__(256) void k_minmax_comps(DLevelView L, DMFView M, M
   }
 }
 
-int pa_ensure_red(pa_ctx* ctx, size_t n);
-
 extern "C" int pa_minmax_comps_level(pa_ctx* ctx, const pa_mf* s, int ncomps, const int32_t* comps, double* mn, double* mx) {
   PaBind bind_(ctx);
   if (!ctx || !s || !comps || !mn || !mx) return pa_fail(ctx, "pa_minmax_comps_level: null argument");

@@ -1,6 +1,6 @@
 // pa_stencil.hip -- gradient / curvature kernels (gfx950).
 // Pass-by-pass kernels mirror the reference call sites one to one; the fused
-// grad->curvature kernel lives in pa_fused.hip.
+// grad->curvature kernel lives in pa_fused_march3.h (launched from pa_fused_sweep.hip).
 #include "pa_internal.h"
 #include "pa_fabview.h"
 #include "pa_grad_march.h"
@@ -145,8 +145,6 @@ __global__ __launch_bounds__(256) void k_minmax(DLevelView L, DMFView M, int com
     part[2 * slot + 1] = hi;
   }
 }
-
-int pa_ensure_red(pa_ctx* ctx, size_t n);
 
 extern "C" int pa_minmax_level(pa_ctx* ctx, const pa_mf* s, int comp, double* mn, double* mx) {
   PaBind bind_(ctx);

@@ -117,7 +117,7 @@ def test_gradcurv_fused_wide_boxes(ctx, oracle, threshold, pipeline, options):
 @pytest.mark.parametrize("threshold", [None, 0.05, 0.3])
 @pytest.mark.parametrize("per,sym", [((1, 1, 0), (0, 0, 0)), ((0, 0, 0), (1, 0, 1)), ((0, 1, 1), (0, 0, 0))])
 def test_gradcurv_exact_normal_pipeline(ctx, oracle, per, sym, threshold):
-    """boxes wider than 32 cells, no threshold, pure special faces: the exact-normal pipeline (pa_fused.hip: the sweep reads
+    """boxes wider than 32 cells, no threshold, pure special faces: the exact-normal pipeline (pa_fused_prep.hip / pa_fused_sweep.hip: the sweep reads
     the resolved ghost c behind coarse-fine / wall faces from compact face-major arrays; only the curvature of the first
     layer behind such a face is fixed up).  3 levels of 48^3 boxes: 4 row tiles per box (3 x 13 + 9 rows), 3 z segments of
     16 planes (interior and end segments), coarse-fine faces in all three directions, every wall type."""
@@ -156,7 +156,7 @@ def test_gradcurv_exact_normal_pipeline(ctx, oracle, per, sym, threshold):
 
 
 def test_clip_fixup_general_path_is_exercised(ctx, oracle):
-    """the clip-aware fix-up's hand-over list (pa_fused.hip: SlowList): a threshold whose iso-surfaces cross the coarse-fine
+    """the clip-aware fix-up's hand-over list (pa_fused_fix.hip: SlowList): a threshold whose iso-surfaces cross the coarse-fine
     faces puts layer-1 cells next to clipped neighbours, which must go through the general path -- and still match the oracle"""
     from peleanalysis_amd.hierarchy import nested_hierarchy, field_flame
     H = nested_hierarchy(96, 3, 48, is_per=(1, 1, 0))
@@ -609,7 +609,7 @@ def test_work_multifabs_are_never_read_before_they_are_written():
 
 @pytest.mark.parametrize("per,sym", [((0, 0, 0), (0, 0, 0)), ((0, 1, 0), (1, 0, 1)), ((1, 0, 1), (0, 0, 0))])
 def test_chunked_face_kernels_odd_origins_small_faces_and_slots(ctx, oracle, per, sym):
-    """The chunk records' corner cases (pa_fused.hip, round 6): level-0 boxes cut on ODD indices (block origins on even global
+    """The chunk records' corner cases (pa_fused_prep.hip / pa_fused_fix.hip, round 6): level-0 boxes cut on ODD indices (block origins on even global
     indices start at -1: cells outside the face are predicated off), extents that are not multiples of anything, faces 3 cells
     wide, wall / reflect-odd / coarse-fine cells in one chunk, a fine level whose faces end in one-sided stencils next to the
     walls -- bit for bit against the oracle, one component at a time and three components in one batch (slot = blockIdx.z)."""
