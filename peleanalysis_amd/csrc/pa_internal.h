@@ -32,8 +32,9 @@ struct pa_options {
                                       // filled with NaN at every acquisition -- a kernel that reads a cell no step of THIS call wrote shows up in the result
   int force_fallbacks = 0;            // PA_FORCE_FALLBACKS=1 (tests): every path that exists for inputs the tuned one does not take -- FillBoundary /
                                       // patch gather per ghost cell (regions that do not fit a plan), the sweeps group by group (more groups than a
-                                      // launch holds), the first form of the marching-cubes cell pass (FABs wider than 819 cells) and its
-                                      // level-by-level loop, FillPatchTwoLevels per ghost cell (ratio != 2), ghost fills level by level -- on ANY input
+                                      // launch holds), the first form of the marching-cubes cell pass (FABs wider than 819 cells; the switch selects
+                                      // that cell pass only, the launch chain behind it is the same), FillPatchTwoLevels per ghost cell (ratio != 2),
+                                      // ghost fills level by level -- on ANY input
 };
 const pa_options& pa_opt();
 

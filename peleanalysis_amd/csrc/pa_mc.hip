@@ -365,13 +365,20 @@ extern "C" int pa_mc_emit_fab(pa_ctx* ctx, pa_box loop, const pa_fab* state, con
 // The state and the mask are level multifabs with the same ghost width, so a cell's index in its
 // grown FAB addresses both, and the per-cell scratch (2 B from the cell pass, 1 B edge bits, 4 B vertex
 // offset) is laid out FAB after FAB, each FAB padded to a whole 256-cell block.
-//   k_mcl_cells     ONE streaming pass over the iso component and the mask (16 B per cell): per cell the byte
-//                   lc = cube is live | own x/y/z edge crosses the iso value << 1, and the cube index; marks
-//                   the 256-cell blocks that contain anything (most of a level does not touch the surface)
-//   k_mcl_count     marked blocks only: edge bits (first live cube that touches the edge) + triangle counts
-//   k_mcl_scan      one workgroup per FAB: exclusive scan of its block sums, FAB totals
-//   k_mcl_lists     marked blocks only: vertex offsets + one work item per vertex / triangle
-//   k_mcl_verts / k_mcl_tris  one thread per vertex / triangle; as k_mc_verts / k_mc_tris, behind the FAB's base
+// One chain of launches (mc_run) for up to PA_MAXB levels at a time; a single-level call is a batch of one level:
+//   cell pass        ONE streaming pass over the iso component and the mask: per cell the byte lc = cube is live | own x/y/z
+//                    edge crosses the iso value << 1, and the cube index; marks the 256-cell blocks that contain anything (most
+//                    of a level does not touch the surface).  Per level one of
+//                      k_mclb_cells4           slab form, mask evaluated in place (8 B per cell), all such levels in one launch
+//                      k_mcl_cells4<512,2,0>   slab form reading a mask multifab (16 B per cell), the level's own launch
+//                      k_mcl_cells<8>          first form (FABs too wide for a slab), the level's own launch
+//   k_mclb_active    list of the marked blocks
+//   k_mclb_count     marked blocks only: edge bits (first live cube that touches the edge) + triangle counts
+//   k_mclb_scan      one workgroup per FAB: exclusive scan of its block sums, FAB totals
+//   k_mclb_base      first vertex / triangle of every FAB in its level's output
+//   k_mclb_lists     marked blocks only: vertex offsets + one work item per vertex / triangle
+//   k_mclb_verts / k_mclb_tris  one thread per vertex / triangle; as k_mc_verts / k_mc_tris, behind the FAB's base
+//   k_mclb_clean     the code bytes of the marked blocks back to zero
 struct MclGeo {
   int slo[3], n[3];
   int llo[3], lhi[3];
@@ -752,7 +759,7 @@ __device__ __forceinline__ void mcl_cells4_body(const MclArgs& A, const unsigned
     // The two code bytes of a cell are stored only where there is something: a cell that owns a crossing edge or whose live
     // cube is cut by the surface.  Every later kernel reads codes of such cells only, or the live bit of a cube that touches
     // a crossing edge -- which is cut if it is live -- so a zero byte stands for the rest.  The scratch that holds the codes
-    // is all zeros between calls (pa_ctx::d_mcz, k_mcl_clean); the pass then writes a few per cent of the level's cells
+    // is all zeros between calls (pa_ctx::d_mcz, k_mclb_clean); the pass then writes a few per cent of the level's cells
     // instead of 2 B for every cell (measured before: 0.28 GB of the pass's 1.47 GB on a 512^3 level).
     if (!act) return;
     if (al4 && OWN[g] == M1) {
@@ -808,7 +815,7 @@ __global__ __launch_bounds__(NT) void k_mcl_cells4(MclArgs A) {
   mcl_cells4_body<NT, GPT, MM>(A, blockIdx.x, s_fl);
 }
 
-// ---- several levels per launch (pa_mc_hierarchy_fine): level l owns workgroups wg0[l] .. wg0[l+1]-1 of a launch (the host
+// ---- several levels per launch: level l owns workgroups wg0[l] .. wg0[l+1]-1 of a launch (the host
 // fills wg0 per kernel: tiles, 1024-block chunks, FABs, vertices / 256, triangles / 256); the persistent kernels walk the
 // levels' marked-block lists one after the other
 struct MclBatch {
@@ -863,7 +870,6 @@ __device__ __forceinline__ void mcl_active_body(const MclArgs& A, int nblk, unsi
   }
 }
 
-__global__ __launch_bounds__(1024) void k_mcl_active(MclArgs A, int nblk) { mcl_active_body(A, nblk, blockIdx.x); }
 __global__ __launch_bounds__(1024) void k_mclb_active(MclBatch Bt) {
   unsigned w;
   const MclArgs A = Bt.a[Bt.find(blockIdx.x, w)];
@@ -930,7 +936,6 @@ __device__ __forceinline__ void mcl_count_body(const MclArgs& A) {
   }
 }
 
-__global__ __launch_bounds__(256) void k_mcl_count(MclArgs A) { mcl_count_body(A); }
 __global__ __launch_bounds__(256) void k_mclb_count(MclBatch Bt) {
   for (int l = 0; l < Bt.n; ++l) {
     const MclArgs A = Bt.a[l];
@@ -967,7 +972,6 @@ __device__ __forceinline__ void mcl_scan_body(const MclArgs& A, const int b) {
   if (t == 1023) { A.tot[2 * b] = s_a[1023]; A.tot[2 * b + 1] = s_b[1023]; }
 }
 
-__global__ __launch_bounds__(1024) void k_mcl_scan(MclArgs A) { mcl_scan_body(A, blockIdx.x); }
 __global__ __launch_bounds__(1024) void k_mclb_scan(MclBatch Bt) {
   unsigned w;
   const MclArgs A = Bt.a[Bt.find(blockIdx.x, w)];
@@ -1002,15 +1006,15 @@ __global__ __launch_bounds__(256) void k_mclb_base(MclBatch Bt) {
   }
 }
 
-// Emission.  k_mcl_lists (marked blocks): vertex offset of every cell (kept for the triangles) and one work item per
+// Emission.  k_mclb_lists (marked blocks): vertex offset of every cell (kept for the triangles) and one work item per
 // vertex / per triangle, parked in the output slot of that vertex (its 24-byte key) / triangle (its 12-byte id triple):
-// (scratch cell, FAB, edge direction or triangle number).  k_mcl_verts / k_mcl_tris then run one thread per item --
+// (scratch cell, FAB, edge direction or triangle number).  k_mclb_verts / k_mclb_tris then run one thread per item --
 // a marked block holds ~3 vertices per 256 cells, so per-block emission left 99 % of the lanes idle behind chains of
-// dependent loads (measured 0.64 + 0.33 ms for 0.46 M vertices + 0.91 M triangles; see DESIGN.md 3.2).
+// dependent loads (measured 0.64 + 0.33 ms for 0.46 M vertices + 0.91 M triangles; see DESIGN.md 3.4).
 __device__ __forceinline__ void mcl_lists_body(const MclArgs& A, int* vkeys, int* tris) {
   const int nact = *A.nact, lane = threadIdx.x & 63;
   const int nwave = gridDim.x * 4;
-  for (int q = blockIdx.x * 4 + (threadIdx.x >> 6); q < nact; q += nwave) {  // one wave per marked block, as k_mcl_count
+  for (int q = blockIdx.x * 4 + (threadIdx.x >> 6); q < nact; q += nwave) {  // one wave per marked block, as k_mclb_count
     const long long blk = A.alist[2 * q];
     const int b = A.alist[2 * q + 1];
     MclGeo G;
@@ -1049,7 +1053,6 @@ __device__ __forceinline__ void mcl_lists_body(const MclArgs& A, int* vkeys, int
   }
 }
 
-__global__ __launch_bounds__(256) void k_mcl_lists(MclArgs A, int* vkeys, int* tris) { mcl_lists_body(A, vkeys, tris); }
 struct MclOut { double* dv[PA_MAXB]; int* dk[PA_MAXB]; int* dt[PA_MAXB]; long long nv[PA_MAXB], nt[PA_MAXB]; };
 __global__ __launch_bounds__(256) void k_mclb_lists(MclBatch Bt, MclOut O) {
   for (int l = 0; l < Bt.n; ++l) {
@@ -1099,9 +1102,6 @@ __device__ __forceinline__ void mcl_verts_body(const MclArgs& A, double* verts, 
   key[0] = i; key[1] = j; key[2] = k; key[3] = hi_i; key[4] = hi_j; key[5] = hi_k;
 }
 
-__global__ __launch_bounds__(256) void k_mcl_verts(MclArgs A, double* verts, int* vkeys, long long nv) {
-  mcl_verts_body(A, verts, vkeys, nv, blockIdx.x * 256LL + threadIdx.x);
-}
 __global__ __launch_bounds__(256) void k_mclb_verts(MclBatch Bt, MclOut O) {
   unsigned w;
   const int l = Bt.find(blockIdx.x, w);
@@ -1140,7 +1140,6 @@ __device__ __forceinline__ void mcl_tris_body(const MclArgs& A, int* tris, long 
   o[0] = out[0]; o[1] = out[1]; o[2] = out[2];
 }
 
-__global__ __launch_bounds__(256) void k_mcl_tris(MclArgs A, int* tris, long long nt) { mcl_tris_body(A, tris, nt, blockIdx.x * 256LL + threadIdx.x); }
 __global__ __launch_bounds__(256) void k_mclb_tris(MclBatch Bt, MclOut O) {
   unsigned w;
   const int l = Bt.find(blockIdx.x, w);
@@ -1159,7 +1158,6 @@ __device__ __forceinline__ void mcl_clean_body(const MclArgs& A) {
   }
 }
 
-__global__ __launch_bounds__(256) void k_mcl_clean(MclArgs A) { mcl_clean_body(A); }
 __global__ __launch_bounds__(256) void k_mclb_clean(MclBatch Bt) {
   for (int l = 0; l < Bt.n; ++l) mcl_clean_body(Bt.a[l]);
 }
@@ -1265,24 +1263,25 @@ extern "C" int pa_msq_level(pa_ctx* ctx, const pa_mf* state, const pa_mf* mask, 
   PaBind bind_(ctx);
   return mc_level_impl(ctx, state, mask, mcomp, loops, isocomp, isoval, nvert, nseg, dev_verts, dev_vkeys, dev_segs, 1);
 }
-// ---- one level's pass in two phases, so that several levels share ONE count read-back, ONE output allocation and ONE final
-// synchronisation (pa_mc_hierarchy_fine); the single-level entry points run the same two phases back to back.
-//   phase 1  cell pass, marked-block list, counts, per-FAB scan; the FAB totals are copied to pinned host memory (async)
-//   -- the caller synchronises once, sums the totals of every level and carves the output block --
-//   phase 2  work lists, vertices, triangles into the level's part of the block
+// ---- one level of a call.  A call has nlev levels (one for the single-level entry points); all of them share ONE set of
+// launches per stage, ONE count read-back and ONE output allocation (mc_run):
+//   stage A  cell pass, marked-block list, counts, per-FAB scan, FAB bases; the FAB totals are copied to pinned host memory (async)
+//   -- mc_run synchronises once, sums the totals of every level and carves the output block --
+//   stage B  work lists, vertices, triangles into the level's part of the block, code bytes back to zero
 struct MclWork {
   MclArgs A;
   const pa_mf* state = nullptr;
   int nb = 0, dim2 = 0;
-  std::vector<long long> coff, base;
+  std::vector<long long> coff;
   std::vector<DBox> dl;
-  size_t ncell = 0, nblk = 0, hdr = 0, bytes = 0;  // scratch of this level
+  size_t ncell = 0, nblk = 0;  // scratch of this level
   long long maxcell = 0, nv = 0, nt = 0;
   int64_t *nvert = nullptr, *ntri = nullptr;
   long long* h_tot = nullptr;                      // [nb][2] in the context's pinned buffer
-  long long* d_base = nullptr;
   double* dv = nullptr; int32_t *dk = nullptr, *dt = nullptr;
-  bool full_codes = false;
+  bool full_codes = false;  // the level takes the first form of the cell pass, which writes the codes of every cell
+  long long wgs = 0;        // workgroups of the slab form of the cell pass
+  bool own_cells() const { return full_codes || !A.nomask; }  // the cell pass is a launch of the level's own, not part of k_mclb_cells4
 };
 
 static int mc_prepare(pa_ctx* ctx, const pa_mf* state, const pa_mf* mask, int mcomp, const pa_box* loops, int isocomp, double isoval, int64_t* nvert, int64_t* ntri,
@@ -1318,14 +1317,12 @@ static int mc_prepare(pa_ctx* ctx, const pa_mf* state, const pa_mf* mask, int mc
     W.coff[b + 1] = W.coff[b] + (on ? (nc + 255) / 256 * 256 : 0);
     nvert[b] = ntri[b] = 0;
   }
-  W.ncell = W.nblk = W.hdr = W.bytes = 0;
+  W.ncell = W.nblk = 0;
   if (nb == 0 || W.maxcell == 0) return 0;
   if (nb > 0x0fffffff) return pa_fail(ctx, "pa_mc_level: too many FABs");
   W.ncell = (size_t)W.coff[nb];
   W.nblk = W.ncell / 256;
   if (W.nblk > 0x7fffffffull) return pa_fail(ctx, "pa_mc_level: level too large for one pass");
-  W.hdr = ((size_t)nb * (16 + 16 + 24) + ((size_t)nb + 1) * 8 + 255) / 256 * 256;
-  W.bytes = (W.hdr + 5 * W.ncell + 17 * W.nblk + 512 + 255) / 256 * 256;  // + 2 B per cell in the context's zeroed code buffer
   MclArgs& A = W.A;
   A.L = L->view; A.S = state->view; A.M = mask->view;
   A.mcomp = mcomp; A.isocomp = isocomp; A.ncomp = state->ncomp; A.iso = isoval;
@@ -1399,83 +1396,57 @@ static const WgTab* mcl_tiletab(const pa_level* L, int ng, int kseg, int cap_cel
   return raw->d ? raw : nullptr;
 }
 
-static int mc_phase1(pa_ctx* ctx, MclWork& W, unsigned char* scr, unsigned char* codes) {
-  if (W.nb == 0 || W.maxcell == 0) return 0;
+constexpr int NT4 = 512, GPT4 = 2;  // slab form of the cell pass: 4096 cells of a plane per workgroup
+// which cell pass a level takes, and the slab geometry of the second form
+static int mc_cells_geometry(pa_ctx* ctx, MclWork& W) {
   const pa_level* L = W.state->lev;
   const int nb = W.nb, ng = W.state->ng;
-  const size_t ncell = W.ncell, nblk = W.nblk;
   MclArgs& A = W.A;
-  unsigned char* p = scr;
-  A.tot = (long long*)p; p += 16 * (size_t)nb;
-  W.d_base = (long long*)p; p += 16 * (size_t)nb;
-  long long* d_coff = (long long*)p; p += 8 * ((size_t)nb + 1);
-  DBox* d_loops = (DBox*)p;
-  p = scr + W.hdr;
-  A.voff = (int*)p; p += 4 * ncell;
-  A.bsum = (int*)p; p += 8 * nblk;
-  A.lc = codes;
-  A.cidx = codes + ncell;
-  A.vflag = p; p += ncell;
-  A.bact = p; p += (nblk + 255) / 256 * 256;
-  A.alist = (int*)p; p += 8 * nblk;
-  A.nact = (int*)p;
-  A.base = W.d_base; A.coff = d_coff; A.loops = d_loops;
-  PA_HIP(hipMemcpyAsync(d_coff, W.coff.data(), 8 * ((size_t)nb + 1), hipMemcpyHostToDevice, ctx->stream));
-  PA_HIP(hipMemcpyAsync(d_loops, W.dl.data(), sizeof(DBox) * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
-  {
-    constexpr int TY = 8;  // tile rows of the first form of the cell pass (FABs too wide for the slab form)
-    const int mx = L->maxn[0] + 2 * ng, my = L->maxn[1] + 2 * ng, mz = L->maxn[2] + 2 * ng;
-    auto tiles = [&](int ty) { return (unsigned)(std::max(1, (mx - 1 + 62) / 63) * std::max(1, (my - 1 + ty - 2) / (ty - 1)) * ((mz + A.kseg - 1) / A.kseg)); };
-    // bact | alist | nact are adjacent and bsum precedes lc: two clears (bsum; bact .. nact)
-    PA_HIP(hipMemsetAsync(A.bsum, 0, 8 * nblk, ctx->stream));
-    PA_HIP(hipMemsetAsync(A.bact, 0, (size_t)((unsigned char*)A.nact - A.bact) + 4, ctx->stream));
-    constexpr int NT4 = 512, GPT4 = 2;  // 4096 cells of a plane per workgroup
-    if ((long long)mx * 5 <= 4LL * NT4 * GPT4 && !pa_opt().force_fallbacks) {
-      // slab = as many whole rows as fit next to their halo row, evened out over the slabs of the largest FAB, multiple of 4
-      const int rmax = std::max(4, ((4 * NT4 * GPT4) / mx - 1) / 4 * 4);
-      const int ns0 = (my + rmax - 1) / rmax;
-      A.rows = std::min(rmax, ((my + ns0 - 1) / ns0 + 3) / 4 * 4);
-      A.nslab = (my + A.rows - 1) / A.rows;
-      {  // enough workgroups for 8 per CU in flight, planes re-read at the segment ends <= 1 in 16
-        const long long want = 6144;
-        const int nseg = (int)std::min<long long>(std::max<long long>(1, mz / 16), std::max<long long>(1, (want + (long long)nb * A.nslab - 1) / ((long long)nb * A.nslab)));
-        A.kseg = (mz + nseg - 1) / nseg;
-      }
-      A.tiles = A.nslab * ((mz + A.kseg - 1) / A.kseg);
-      A.ldsw = NT4 * GPT4 + (mx >> 2) + 4;
-      if (const WgTab* tt = mcl_tiletab(L, ng, A.kseg, 4 * NT4 * GPT4)) { A.tiletab = tt->d; A.ntab = tt->n; }
-      const long long total = A.tiletab ? (long long)A.ntab : (long long)nb * A.tiles;
-      if (total > 0x7ffffff0LL) return pa_fail(ctx, "pa_mc_level: level too large for one pass");
-      const dim3 g4((unsigned)((total + 7) / 8 * 8));
-      const size_t lds4 = 2 * (size_t)A.ldsw * 4;
-      if (!A.nomask) hipLaunchKernelGGL((k_mcl_cells4<NT4, GPT4, 0>), g4, dim3(NT4), lds4, ctx->stream, A);
-      else if (!A.has_fine) hipLaunchKernelGGL((k_mcl_cells4<NT4, GPT4, 1>), g4, dim3(NT4), lds4, ctx->stream, A);
-      else hipLaunchKernelGGL((k_mcl_cells4<NT4, GPT4, 2>), g4, dim3(NT4), lds4, ctx->stream, A);
-    } else {
-      W.full_codes = true;  // the first form writes the codes of every cell: the code buffer is cleared as a whole afterwards
-      hipLaunchKernelGGL((k_mcl_cells<TY>), dim3(tiles(TY), (unsigned)nb), dim3(64 * TY), 0, ctx->stream, A);
-    }
-    hipLaunchKernelGGL(k_mcl_active, dim3((unsigned)((nblk + 1023) / 1024)), dim3(1024), 0, ctx->stream, A, (int)nblk);
+  const int mx = L->maxn[0] + 2 * ng, my = L->maxn[1] + 2 * ng, mz = L->maxn[2] + 2 * ng;
+  W.full_codes = (long long)mx * 5 > 4LL * NT4 * GPT4 || pa_opt().force_fallbacks;  // the first form writes the codes of every cell
+  if (W.full_codes) return 0;
+  // slab = as many whole rows as fit next to their halo row, evened out over the slabs of the largest FAB, multiple of 4
+  const int rmax = std::max(4, ((4 * NT4 * GPT4) / mx - 1) / 4 * 4);
+  const int ns0 = (my + rmax - 1) / rmax;
+  A.rows = std::min(rmax, ((my + ns0 - 1) / ns0 + 3) / 4 * 4);
+  A.nslab = (my + A.rows - 1) / A.rows;
+  {  // enough workgroups for 8 per CU in flight, planes re-read at the segment ends <= 1 in 16
+    const long long want = 6144;
+    const int nseg = (int)std::min<long long>(std::max<long long>(1, mz / 16), std::max<long long>(1, (want + (long long)nb * A.nslab - 1) / ((long long)nb * A.nslab)));
+    A.kseg = (mz + nseg - 1) / nseg;
   }
-  const dim3 grid(4096);  // persistent over the marked blocks
-  hipLaunchKernelGGL(k_mcl_count, grid, dim3(256), 0, ctx->stream, A);
-  hipLaunchKernelGGL(k_mcl_scan, dim3((unsigned)nb), dim3(1024), 0, ctx->stream, A);
-  PA_HIP(hipGetLastError());
-  PA_HIP(hipMemcpyAsync(W.h_tot, A.tot, 16 * (size_t)nb, hipMemcpyDeviceToHost, ctx->stream));
+  A.tiles = A.nslab * ((mz + A.kseg - 1) / A.kseg);
+  A.ldsw = NT4 * GPT4 + (mx >> 2) + 4;
+  if (const WgTab* tt = mcl_tiletab(L, ng, A.kseg, 4 * NT4 * GPT4)) { A.tiletab = tt->d; A.ntab = tt->n; }
+  const long long total = A.tiletab ? (long long)A.ntab : (long long)nb * A.tiles;
+  if (total > 0x7ffffff0LL) return pa_fail(ctx, "pa_mc_level: level too large for one pass");
+  W.wgs = (total + 7) / 8 * 8;
   return 0;
 }
+// the cell pass of a level that is not part of k_mclb_cells4: the slab form reading a mask multifab, or the first form (FABs too
+// wide for a slab, PA_FORCE_FALLBACKS=1)
+static void mc_cells_own(pa_ctx* ctx, const MclWork& W) {
+  const MclArgs& A = W.A;
+  if (!W.full_codes) {
+    hipLaunchKernelGGL((k_mcl_cells4<NT4, GPT4, 0>), dim3((unsigned)W.wgs), dim3(NT4), 2 * (size_t)A.ldsw * 4, ctx->stream, A);
+    return;
+  }
+  constexpr int TY = 8;  // tile rows
+  const pa_level* L = W.state->lev;
+  const int ng = W.state->ng, mx = L->maxn[0] + 2 * ng, my = L->maxn[1] + 2 * ng, mz = L->maxn[2] + 2 * ng;
+  const unsigned tiles = (unsigned)(std::max(1, (mx - 1 + 62) / 63) * std::max(1, (my - 1 + TY - 2) / (TY - 1)) * ((mz + A.kseg - 1) / A.kseg));
+  hipLaunchKernelGGL((k_mcl_cells<TY>), dim3(tiles, (unsigned)W.nb), dim3(64 * TY), 0, ctx->stream, A);
+}
 
-// after the synchronisation: per-FAB counts of this level, its bases inside its part of the output
+// after the synchronisation: per-FAB counts of this level
 static int mc_counts(pa_ctx* ctx, MclWork& W) {
   W.nv = W.nt = 0;
   if (W.nb == 0 || W.maxcell == 0) return 0;
-  W.base.assign(2 * (size_t)W.nb, 0);
   for (int b = 0; b < W.nb; ++b) {
     const bool on = W.coff[b + 1] > W.coff[b];
     W.nvert[b] = on ? W.h_tot[2 * b] : 0;
     W.ntri[b] = on ? W.h_tot[2 * b + 1] : 0;
     if (W.nvert[b] > 0x7fffffffLL || W.ntri[b] > 0x7fffffffLL / 3) return pa_fail(ctx, "pa_mc_level: surface of one FAB too large for 32-bit ids");
-    W.base[2 * b] = W.nv; W.base[2 * b + 1] = W.nt;
     W.nv += W.nvert[b]; W.nt += W.ntri[b];
   }
   return 0;
@@ -1485,22 +1456,6 @@ static void mc_parts(const MclWork& W, size_t& bv, size_t& bk, size_t& bt) {
   bv = ((size_t)W.nv * W.A.ncomp * 8 + 255) / 256 * 256;
   bk = ((size_t)W.nv * 24 + 255) / 256 * 256;
   bt = (std::max<size_t>(8, (size_t)W.nt * 12) + 255) / 256 * 256;
-}
-
-static int mc_phase2(pa_ctx* ctx, MclWork& W, unsigned char* part) {
-  if (W.nv == 0 && W.nt == 0) return 0;
-  size_t bv, bk, bt;
-  mc_parts(W, bv, bk, bt);
-  W.dv = (double*)part;
-  W.dk = (int32_t*)(part + bv);
-  W.dt = (int32_t*)(part + bv + bk);
-  PA_HIP(hipMemcpyAsync(W.d_base, W.base.data(), 16 * (size_t)W.nb, hipMemcpyHostToDevice, ctx->stream));
-  const dim3 grid(4096);
-  hipLaunchKernelGGL(k_mcl_lists, grid, dim3(256), 0, ctx->stream, W.A, W.dk, W.dt);
-  if (W.nv > 0) hipLaunchKernelGGL(k_mcl_verts, dim3((unsigned)((W.nv + 255) / 256)), dim3(256), 0, ctx->stream, W.A, W.dv, W.dk, W.nv);
-  if (W.nt > 0) hipLaunchKernelGGL(k_mcl_tris, dim3((unsigned)((W.nt + 255) / 256)), dim3(256), 0, ctx->stream, W.A, W.dt, W.nt);
-  PA_HIP(hipGetLastError());
-  return 0;
 }
 
 // the output block: a cached one that fits without wasting more than half of itself, else a new one (freed by pa_device_free)
@@ -1527,158 +1482,19 @@ static unsigned char* mc_block(pa_ctx* ctx, size_t need) {
   return blockp;
 }
 
-static_assert(sizeof(MclBatch) + sizeof(MclOut) <= 4000, "kernel arguments of the batched marching-cubes kernels");
-
-// The levels of a hierarchy through ONE set of launches (k_mclb_*): one upload of the levels' tables, one clear, one launch per
-// stage for all levels, one read-back of the FAB totals, the FAB bases computed on the device, no final synchronisation (the
-// results are complete in stream order: pa_memcpy_d2h and every later call on the context wait for them).
-// Scratch: [C: per level coff | loops][T: per level tot][B: per level base][Z: per level bsum | bact | alist | nact][R: per level voff | vflag]
-static int mc_run_batched(pa_ctx* ctx, int nlev, MclWork* W) {
-  constexpr int NT4 = 512, GPT4 = 2;
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  size_t cb = 0, tb = 0, zb = 0, rb = 0, ncodes = 0;
-  for (int l = 0; l < nlev; ++l) {
-    const size_t nb = (size_t)W[l].nb;
-    cb += al(8 * (nb + 1) + sizeof(DBox) * nb);
-    tb += 16 * nb;
-    zb += al(8 * W[l].nblk) + al(W[l].nblk) + al(8 * W[l].nblk) + 256;
-    rb += al(4 * W[l].ncell) + al(W[l].ncell);
-    ncodes += 2 * W[l].ncell;
-  }
-  tb = al(tb);
-  const size_t bb = tb;
-  if (ensure_scr(ctx, cb + tb + bb + zb + rb)) return 1;
-  PA_TRY_RET(upload_tables(ctx));
-  unsigned char* pin = (unsigned char*)mc_pinned(ctx, (cb + tb) / sizeof(long long) + 8);
-  if (!pin) return 1;
-  if (ctx->mcz_cap < ncodes) {
-    if (ctx->d_mcz) (void)hipFree(ctx->d_mcz);
-    ctx->d_mcz = nullptr; ctx->mcz_cap = 0;
-    PA_HIP(hipMalloc(&ctx->d_mcz, ncodes));
-    ctx->mcz_cap = ncodes;
-    ctx->mcz_dirty = true;
-  }
-  if (ctx->mcz_dirty) PA_HIP(hipMemsetAsync(ctx->d_mcz, 0, ctx->mcz_cap, ctx->stream));
-  ctx->mcz_dirty = true;
-  unsigned char* const S = (unsigned char*)ctx->d_scr;
-  unsigned char *pc = S, *pt = S + cb, *pb = S + cb + tb, *pz = S + cb + tb + bb, *pr = S + cb + tb + bb + zb, *pcode = (unsigned char*)ctx->d_mcz;
-  unsigned char* hc = pin;  // host image of region C
-  MclBatch Bt;
-  Bt.n = nlev;
-  size_t ldsw = 0;
-  for (int l = 0; l < nlev; ++l) {
-    MclWork& w = W[l];
-    MclArgs& A = w.A;
-    const size_t nb = (size_t)w.nb;
-    const pa_level* L = w.state->lev;
-    const int ng = w.state->ng;
-    std::memcpy(hc, w.coff.data(), 8 * (nb + 1));
-    std::memcpy(hc + 8 * (nb + 1), w.dl.data(), sizeof(DBox) * nb);
-    A.coff = (const long long*)pc;
-    A.loops = (const DBox*)(pc + 8 * (nb + 1));
-    pc += al(8 * (nb + 1) + sizeof(DBox) * nb); hc += al(8 * (nb + 1) + sizeof(DBox) * nb);
-    A.tot = (long long*)pt; w.h_tot = (long long*)(pin + cb + (pt - (S + cb))); pt += 16 * nb;
-    w.d_base = (long long*)pb; A.base = w.d_base; pb += 16 * nb;
-    A.bsum = (int*)pz; pz += al(8 * w.nblk);
-    A.bact = pz; pz += al(w.nblk);
-    A.alist = (int*)pz; pz += al(8 * w.nblk);
-    A.nact = (int*)pz; pz += 256;
-    A.voff = (int*)pr; pr += al(4 * w.ncell);
-    A.vflag = pr; pr += al(w.ncell);
-    A.lc = pcode; A.cidx = pcode + w.ncell; pcode += 2 * w.ncell;
-    // slab form of the cell pass (as mc_phase1)
-    const int mx = L->maxn[0] + 2 * ng, my = L->maxn[1] + 2 * ng, mz = L->maxn[2] + 2 * ng;
-    const int rmax = std::max(4, ((4 * NT4 * GPT4) / mx - 1) / 4 * 4);
-    const int ns0 = (my + rmax - 1) / rmax;
-    A.rows = std::min(rmax, ((my + ns0 - 1) / ns0 + 3) / 4 * 4);
-    A.nslab = (my + A.rows - 1) / A.rows;
-    {
-      const long long want = 6144;
-      const int nseg = (int)std::min<long long>(std::max<long long>(1, mz / 16), std::max<long long>(1, (want + (long long)nb * A.nslab - 1) / ((long long)nb * A.nslab)));
-      A.kseg = (mz + nseg - 1) / nseg;
-    }
-    A.tiles = A.nslab * ((mz + A.kseg - 1) / A.kseg);
-    A.ldsw = NT4 * GPT4 + (mx >> 2) + 4;
-    if (const WgTab* tt = mcl_tiletab(L, ng, A.kseg, 4 * NT4 * GPT4)) { A.tiletab = tt->d; A.ntab = tt->n; }
-    ldsw = std::max(ldsw, (size_t)A.ldsw);
-    Bt.a[l] = A;
-  }
-  ProfScope prof(ctx, PA_TAG_MC);
-  PA_HIP(hipMemcpyAsync(S, pin, cb, hipMemcpyHostToDevice, ctx->stream));
-  PA_HIP(hipMemsetAsync(S + cb + tb + bb, 0, zb, ctx->stream));
-  auto ranges = [&](auto count) {  // wg0 of a launch from the levels' workgroup counts
-    Bt.wg0[0] = 0;
-    for (int l = 0; l < nlev; ++l) Bt.wg0[l + 1] = Bt.wg0[l] + (unsigned)count(l);
-    return Bt.wg0[nlev];
-  };
-  unsigned g = ranges([&](int l) { return ((W[l].A.tiletab ? (long long)W[l].A.ntab : (long long)W[l].nb * W[l].A.tiles) + 7) / 8 * 8; });
-  hipLaunchKernelGGL((k_mclb_cells4<NT4, GPT4>), dim3(g), dim3(NT4), 2 * ldsw * 4, ctx->stream, Bt);
-  g = ranges([&](int l) { return (W[l].nblk + 1023) / 1024; });
-  hipLaunchKernelGGL(k_mclb_active, dim3(g), dim3(1024), 0, ctx->stream, Bt);
-  hipLaunchKernelGGL(k_mclb_count, dim3(4096), dim3(256), 0, ctx->stream, Bt);
-  g = ranges([&](int l) { return W[l].nb; });
-  hipLaunchKernelGGL(k_mclb_scan, dim3(g), dim3(1024), 0, ctx->stream, Bt);
-  hipLaunchKernelGGL(k_mclb_base, dim3((unsigned)nlev), dim3(256), 0, ctx->stream, Bt);
-  PA_HIP(hipGetLastError());
-  PA_HIP(hipMemcpyAsync(pin + cb, S + cb, tb, hipMemcpyDeviceToHost, ctx->stream));
-  PA_HIP(hipStreamSynchronize(ctx->stream));  // the ONE read-back: FAB totals of every level
-  size_t need = 0;
-  for (int l = 0; l < nlev; ++l) {
-    if (mc_counts(ctx, W[l])) return 1;
-    if (W[l].nv || W[l].nt) { size_t bv, bk, bt; mc_parts(W[l], bv, bk, bt); need += bv + bk + bt; }
-  }
-  MclOut O;
-  unsigned char* blockp = nullptr;
-  if (need > 0) {
-    blockp = mc_block(ctx, need);
-    if (!blockp) return 1;
-    size_t off = 0;
-    for (int l = 0; l < nlev; ++l) {
-      O.dv[l] = nullptr; O.dk[l] = nullptr; O.dt[l] = nullptr; O.nv[l] = W[l].nv; O.nt[l] = W[l].nt;
-      if (!(W[l].nv || W[l].nt)) continue;
-      size_t bv, bk, bt;
-      mc_parts(W[l], bv, bk, bt);
-      W[l].dv = (double*)(blockp + off); W[l].dk = (int32_t*)(blockp + off + bv); W[l].dt = (int32_t*)(blockp + off + bv + bk);
-      O.dv[l] = W[l].dv; O.dk[l] = W[l].dk; O.dt[l] = W[l].dt;
-      off += bv + bk + bt;
-    }
-    hipLaunchKernelGGL(k_mclb_lists, dim3(4096), dim3(256), 0, ctx->stream, Bt, O);
-    g = ranges([&](int l) { return (W[l].nv + 255) / 256; });
-    if (g) hipLaunchKernelGGL(k_mclb_verts, dim3(g), dim3(256), 0, ctx->stream, Bt, O);
-    g = ranges([&](int l) { return (W[l].nt + 255) / 256; });
-    if (g) hipLaunchKernelGGL(k_mclb_tris, dim3(g), dim3(256), 0, ctx->stream, Bt, O);
-  }
-  hipLaunchKernelGGL(k_mclb_clean, dim3(1024), dim3(256), 0, ctx->stream, Bt);
-  if (hipGetLastError() != hipSuccess) {  // as mc_run's bail: the pooled block goes back, the levels' pointers are cleared
-    if (blockp) { ctx->surf_live.erase(blockp); (void)hipFree(blockp); }
-    for (int l = 0; l < nlev; ++l) { W[l].dv = nullptr; W[l].dk = W[l].dt = nullptr; }
-    return pa_fail(ctx, "pa_mc_hierarchy_fine: emit kernels failed");
-  }
-  ctx->mcz_dirty = false;
-  return 0;
+// a failed call gives its output block back and clears the levels' pointers
+static int mc_drop(pa_ctx* ctx, int nlev, MclWork* W, unsigned char* blockp, const std::string& msg) {
+  if (blockp) { ctx->surf_live.erase(blockp); (void)hipFree(blockp); }
+  for (int l = 0; l < nlev; ++l) { W[l].dv = nullptr; W[l].dk = W[l].dt = nullptr; }
+  return pa_fail(ctx, msg);
 }
 
-// nlev levels (one for the single-level entry points): see MclWork
-static int mc_run(pa_ctx* ctx, int nlev, MclWork* W) {
-  {  // all levels in one set of launches when each of them takes the slab form of the cell pass with the mask evaluated in place
-    bool batched = nlev > 1 && nlev <= PA_MAXB && !pa_opt().force_fallbacks;
-    for (int l = 0; l < nlev && batched; ++l) {
-      const int mx = W[l].state->lev->maxn[0] + 2 * W[l].state->ng;
-      batched = W[l].nb > 0 && W[l].maxcell > 0 && W[l].A.nomask && !W[l].dim2 && (long long)mx * 5 <= 4LL * 512 * 2;
-    }
-    if (batched) return mc_run_batched(ctx, nlev, W);
-  }
-  size_t scr = 0, npin = 0;
-  for (int l = 0; l < nlev; ++l) { scr += W[l].bytes; npin += 2 * (size_t)W[l].nb; }
-  if (scr == 0) return 0;
-  PA_TRY_RET(upload_tables(ctx));
-  if (ensure_scr(ctx, scr)) return 1;
-  long long* pin = mc_pinned(ctx, npin);
-  if (!pin) return 1;
-  // the code bytes (2 per cell) live in a buffer that is all zeros between calls: cleared when it is (re)allocated or when a
-  // call left it dirty (an error between the cell pass and the clean-up), otherwise only the marked blocks are reset
-  size_t ncodes = 0;
-  for (int l = 0; l < nlev; ++l) ncodes += 2 * W[l].ncell;
+static_assert(sizeof(MclBatch) + sizeof(MclOut) <= 4000, "kernel arguments of the batched marching-cubes kernels");
+
+// the code bytes (2 per cell) live in a buffer that is all zeros between calls: cleared when it is (re)allocated or when a call
+// left it dirty (an error between the cell pass and the clean-up, or a level on the first form of the cell pass), otherwise
+// only the marked blocks are reset (k_mclb_clean)
+static int mc_codes(pa_ctx* ctx, size_t ncodes) {
   if (ctx->mcz_cap < ncodes) {
     if (ctx->d_mcz) (void)hipFree(ctx->d_mcz);
     ctx->d_mcz = nullptr; ctx->mcz_cap = 0;
@@ -1688,41 +1504,133 @@ static int mc_run(pa_ctx* ctx, int nlev, MclWork* W) {
   }
   if (ctx->mcz_dirty) PA_HIP(hipMemsetAsync(ctx->d_mcz, 0, ctx->mcz_cap, ctx->stream));
   ctx->mcz_dirty = true;  // until the clean-up of this call is enqueued
+  return 0;
+}
+
+// nlev levels (one for the single-level entry points) through ONE set of launches (k_mclb_*): one upload of the levels' tables,
+// one clear, one launch per stage for up to PA_MAXB levels (more levels: chunks of PA_MAXB, stage A of every chunk before the
+// read-back, stage B of every chunk after it), one read-back of the FAB totals, one output block, the FAB bases computed on the
+// device, no final synchronisation (the results are complete in stream order: pa_memcpy_d2h and every later call on the context
+// wait for them).  Levels without work (no FAB, or only empty loop boxes) are left out.
+// Scratch: [C: per level coff | loops][T: per level tot][B: per level base][Z: per level bsum | bact | alist | nact][R: per level voff | vflag]
+static int mc_run(pa_ctx* ctx, const char* name, int nlev, MclWork* W) {
+  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
+  std::vector<MclWork*> act;
+  for (int l = 0; l < nlev; ++l)
+    if (W[l].nb > 0 && W[l].maxcell > 0) act.push_back(&W[l]);
+  if (act.empty()) return 0;
+  size_t cb = 0, tb = 0, zb = 0, rb = 0, ncodes = 0;
+  for (const MclWork* w : act) {
+    const size_t nb = (size_t)w->nb;
+    cb += al(8 * (nb + 1) + sizeof(DBox) * nb);
+    tb += 16 * nb;
+    zb += al(8 * w->nblk) + al(w->nblk) + al(8 * w->nblk) + 256;
+    rb += al(4 * w->ncell) + al(w->ncell);
+    ncodes += 2 * w->ncell;
+  }
+  tb = al(tb);
+  const size_t bb = tb;
+  if (ensure_scr(ctx, cb + tb + bb + zb + rb)) return 1;
+  PA_TRY_RET(upload_tables(ctx));
+  unsigned char* pin = (unsigned char*)mc_pinned(ctx, (cb + tb) / sizeof(long long) + 8);
+  if (!pin) return 1;
+  PA_TRY_RET(mc_codes(ctx, ncodes));
+  unsigned char* const S = (unsigned char*)ctx->d_scr;
+  unsigned char *pc = S, *pt = S + cb, *pb = S + cb + tb, *pz = S + cb + tb + bb, *pr = S + cb + tb + bb + zb, *pcode = (unsigned char*)ctx->d_mcz;
+  unsigned char* hc = pin;  // host image of region C
+  const int nchunk = ((int)act.size() + PA_MAXB - 1) / PA_MAXB;
+  std::vector<MclBatch> B((size_t)nchunk);
+  bool full = false;
+  for (size_t i = 0; i < act.size(); ++i) {
+    MclWork& w = *act[i];
+    MclArgs& A = w.A;
+    const size_t nb = (size_t)w.nb;
+    std::memcpy(hc, w.coff.data(), 8 * (nb + 1));
+    std::memcpy(hc + 8 * (nb + 1), w.dl.data(), sizeof(DBox) * nb);
+    A.coff = (const long long*)pc;
+    A.loops = (const DBox*)(pc + 8 * (nb + 1));
+    pc += al(8 * (nb + 1) + sizeof(DBox) * nb); hc += al(8 * (nb + 1) + sizeof(DBox) * nb);
+    A.tot = (long long*)pt; w.h_tot = (long long*)(pin + cb + (pt - (S + cb))); pt += 16 * nb;
+    A.base = (long long*)pb; pb += 16 * nb;
+    A.bsum = (int*)pz; pz += al(8 * w.nblk);
+    A.bact = pz; pz += al(w.nblk);
+    A.alist = (int*)pz; pz += al(8 * w.nblk);
+    A.nact = (int*)pz; pz += 256;
+    A.voff = (int*)pr; pr += al(4 * w.ncell);
+    A.vflag = pr; pr += al(w.ncell);
+    A.lc = pcode; A.cidx = pcode + w.ncell; pcode += 2 * w.ncell;
+    PA_TRY_RET(mc_cells_geometry(ctx, w));
+    full = full || w.full_codes;
+    MclBatch& Bt = B[i / PA_MAXB];
+    Bt.n = (int)(i % PA_MAXB) + 1;
+    Bt.a[i % PA_MAXB] = A;
+  }
   ProfScope prof(ctx, PA_TAG_MC);
-  size_t so = 0, po = 0, co = 0;
-  for (int l = 0; l < nlev; ++l) {
-    W[l].h_tot = pin + po;
-    if (mc_phase1(ctx, W[l], (unsigned char*)ctx->d_scr + so, (unsigned char*)ctx->d_mcz + co)) return 1;
-    so += W[l].bytes; po += 2 * (size_t)W[l].nb; co += 2 * W[l].ncell;
-  }
-  auto clean = [&]() {  // enqueue the reset of the code buffer (after the last reader)
-    bool full = false;
-    for (int l = 0; l < nlev; ++l) full = full || W[l].full_codes;
-    if (full) return;  // stays dirty: the next call clears everything
-    for (int l = 0; l < nlev; ++l)
-      if (W[l].nb && W[l].maxcell) hipLaunchKernelGGL(k_mcl_clean, dim3(1024), dim3(256), 0, ctx->stream, W[l].A);
-    if (hipGetLastError() == hipSuccess) ctx->mcz_dirty = false;
+  PA_HIP(hipMemcpyAsync(S, pin, cb, hipMemcpyHostToDevice, ctx->stream));
+  PA_HIP(hipMemsetAsync(S + cb + tb + bb, 0, zb, ctx->stream));
+  auto lev = [&](int c, int i) -> MclWork& { return *act[(size_t)c * PA_MAXB + i]; };  // level i of chunk c
+  auto ranges = [&](int c, auto count) {  // wg0 of a launch of chunk c from its levels' workgroup counts
+    MclBatch& Bt = B[c];
+    Bt.wg0[0] = 0;
+    for (int i = 0; i < Bt.n; ++i) Bt.wg0[i + 1] = Bt.wg0[i] + (unsigned)count(lev(c, i));
+    return Bt.wg0[Bt.n];
   };
-  PA_HIP(hipStreamSynchronize(ctx->stream));  // the ONE count read-back (coff / dl are host vectors of this call)
+  for (int c = 0; c < nchunk; ++c) {  // stage A
+    const MclBatch& Bt = B[c];
+    // the cell pass: the levels whose mask is evaluated in place share a launch of the slab form, the others get their own
+    size_t ldsw = 0;
+    for (int i = 0; i < Bt.n; ++i) {
+      if (lev(c, i).own_cells()) mc_cells_own(ctx, lev(c, i));
+      else ldsw = std::max(ldsw, (size_t)Bt.a[i].ldsw);
+    }
+    unsigned g = ranges(c, [](const MclWork& w) { return w.own_cells() ? 0 : w.wgs; });
+    if (g) hipLaunchKernelGGL((k_mclb_cells4<NT4, GPT4>), dim3(g), dim3(NT4), 2 * ldsw * 4, ctx->stream, Bt);
+    g = ranges(c, [](const MclWork& w) { return (w.nblk + 1023) / 1024; });
+    hipLaunchKernelGGL(k_mclb_active, dim3(g), dim3(1024), 0, ctx->stream, Bt);
+    hipLaunchKernelGGL(k_mclb_count, dim3(4096), dim3(256), 0, ctx->stream, Bt);
+    g = ranges(c, [](const MclWork& w) { return w.nb; });
+    hipLaunchKernelGGL(k_mclb_scan, dim3(g), dim3(1024), 0, ctx->stream, Bt);
+    hipLaunchKernelGGL(k_mclb_base, dim3((unsigned)Bt.n), dim3(256), 0, ctx->stream, Bt);
+    PA_HIP(hipGetLastError());
+  }
+  PA_HIP(hipMemcpyAsync(pin + cb, S + cb, tb, hipMemcpyDeviceToHost, ctx->stream));  // region T; h_tot mirrors it
+  PA_HIP(hipStreamSynchronize(ctx->stream));  // the ONE read-back: FAB totals of every level
   size_t need = 0;
-  for (int l = 0; l < nlev; ++l) {
-    if (mc_counts(ctx, W[l])) return 1;
-    if (W[l].nv || W[l].nt) { size_t bv, bk, bt; mc_parts(W[l], bv, bk, bt); need += bv + bk + bt; }
+  for (MclWork* w : act) {
+    if (mc_counts(ctx, *w)) return 1;
+    if (w->nv || w->nt) { size_t bv, bk, bt; mc_parts(*w, bv, bk, bt); need += bv + bk + bt; }
   }
-  if (need == 0) { clean(); return 0; }
-  unsigned char* blockp = mc_block(ctx, need);
-  if (!blockp) return 1;
-  auto bail = [&](const std::string& m) { ctx->surf_live.erase(blockp); (void)hipFree(blockp); for (int l = 0; l < nlev; ++l) { W[l].dv = nullptr; W[l].dk = W[l].dt = nullptr; } return pa_fail(ctx, m); };
+  unsigned char* blockp = nullptr;
+  if (need > 0) {
+    blockp = mc_block(ctx, need);
+    if (!blockp) return 1;
+  }
   size_t off = 0;
-  for (int l = 0; l < nlev; ++l) {
-    if (!(W[l].nv || W[l].nt)) continue;
-    if (mc_phase2(ctx, W[l], blockp + off)) return bail("pa_mc_level: emit kernels failed: " + ctx->err);
-    size_t bv, bk, bt;
-    mc_parts(W[l], bv, bk, bt);
-    off += bv + bk + bt;
+  for (int c = 0; c < nchunk; ++c) {  // stage B
+    const MclBatch& Bt = B[c];
+    MclOut O = {};
+    for (int i = 0; i < Bt.n; ++i) {
+      MclWork& w = lev(c, i);
+      O.nv[i] = w.nv; O.nt[i] = w.nt;
+      if (!(w.nv || w.nt)) continue;
+      size_t bv, bk, bt;
+      mc_parts(w, bv, bk, bt);
+      O.dv[i] = w.dv = (double*)(blockp + off);
+      O.dk[i] = w.dk = (int32_t*)(blockp + off + bv);
+      O.dt[i] = w.dt = (int32_t*)(blockp + off + bv + bk);
+      off += bv + bk + bt;
+    }
+    if (blockp) {
+      hipLaunchKernelGGL(k_mclb_lists, dim3(4096), dim3(256), 0, ctx->stream, Bt, O);
+      unsigned g = ranges(c, [](const MclWork& w) { return (w.nv + 255) / 256; });
+      if (g) hipLaunchKernelGGL(k_mclb_verts, dim3(g), dim3(256), 0, ctx->stream, Bt, O);
+      g = ranges(c, [](const MclWork& w) { return (w.nt + 255) / 256; });
+      if (g) hipLaunchKernelGGL(k_mclb_tris, dim3(g), dim3(256), 0, ctx->stream, Bt, O);
+    }
+    if (!full) hipLaunchKernelGGL(k_mclb_clean, dim3(1024), dim3(256), 0, ctx->stream, Bt);  // else the buffer stays dirty: the next call clears it whole
   }
-  clean();
-  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return bail("pa_mc_level: emit kernels failed");  // base vectors are host memory of this call
+  if (hipGetLastError() != hipSuccess) return mc_drop(ctx, nlev, W, blockp, std::string(name) + ": emit kernels failed");
+  if (!full) ctx->mcz_dirty = false;
   return 0;
 }
 
@@ -1732,61 +1640,55 @@ static int mc_level_impl(pa_ctx* ctx, const pa_mf* state, const pa_mf* mask, int
   *dev_verts = nullptr; *dev_vkeys = nullptr; *dev_tris = nullptr;
   MclWork W;
   if (mc_prepare(ctx, state, mask, mcomp, loops, isocomp, isoval, nvert, ntri, dim2, nomask, fine, ratio, W)) return 1;
-  if (mc_run(ctx, 1, &W)) return 1;
+  if (mc_run(ctx, "pa_mc_level", 1, &W)) return 1;
+  // the single-level calls are synchronous.  (W.dv is the block: the vertex array is the first part of the one level's block,
+  // and a level with any surface has one; null: nothing was allocated)
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return mc_drop(ctx, 1, &W, (unsigned char*)W.dv, "pa_mc_level: emit kernels failed");
   *dev_verts = W.dv; *dev_vkeys = W.dk; *dev_tris = W.dt;  // one allocation, base = the vertex array
   return 0;
 }
 
 // isosurface.cpp:1434-1728 for ALL levels in one call: every level's cell pass / counts are enqueued back to back, the counts
-// of the whole hierarchy are read back ONCE, every level's surface goes into ONE pooled allocation (*block, freed with
-// pa_device_free; dev_verts[l] / dev_vkeys[l] / dev_tris[l] point into it, null for a level without surface) and the host
-// waits once at the end.  states[l] on level l, masked by level l + 1 (fine_mask[l] != 0, isosurface.cpp:1540-1563) or not
-// at all; loops / nvert / ntri: per level, as pa_mc_level_fine.
-// pa_mc_hierarchy_fine on states WITHOUT coordinate components (see MclArgs::xyz)
-extern "C" int pa_mc_hierarchy_xyz(pa_ctx* ctx, int nlev, const pa_mf* const* fields, const int32_t* fine_mask, int ratio, const pa_box* const* loops, int isocomp,
-                                   double isoval, int64_t* const* nvert, int64_t* const* ntri, double** dev_verts, int32_t** dev_vkeys, int32_t** dev_tris, void** block) {
-  PaBind bind_(ctx);
-  if (!ctx || nlev <= 0 || !fields || !loops || !nvert || !ntri || !dev_verts || !dev_vkeys || !dev_tris || !block) return pa_fail(ctx, "pa_mc_hierarchy_xyz: null argument");
-  if (ratio < 2) return pa_fail(ctx, "pa_mc_hierarchy_xyz: bad refinement ratio");
+// of the whole hierarchy are read back ONCE and every level's surface goes into ONE pooled allocation (*block, freed with
+// pa_device_free; dev_verts[l] / dev_vkeys[l] / dev_tris[l] point into it, null for a level without surface); the call returns
+// with the results complete in stream order.  states[l] on level l, masked by level l + 1 (fine_mask[l] != 0,
+// isosurface.cpp:1540-1563) or not at all; loops / nvert / ntri: per level, as pa_mc_level_fine.
+// xyz != 0: the states hold NO coordinate components (see MclArgs::xyz)
+static int mc_hierarchy_impl(pa_ctx* ctx, const std::string& name, int xyz, int nlev, const pa_mf* const* states, const int32_t* fine_mask, int ratio,
+                             const pa_box* const* loops, int isocomp, double isoval, int64_t* const* nvert, int64_t* const* ntri, double** dev_verts,
+                             int32_t** dev_vkeys, int32_t** dev_tris, void** block) {
+  if (!ctx || nlev <= 0 || !states || !loops || !nvert || !ntri || !dev_verts || !dev_vkeys || !dev_tris || !block) return pa_fail(ctx, name + ": null argument");
+  if (ratio < (xyz ? 2 : 1)) return pa_fail(ctx, name + ": bad refinement ratio");
   *block = nullptr;
   std::vector<MclWork> W((size_t)nlev);
   for (int l = 0; l < nlev; ++l) {
     dev_verts[l] = nullptr; dev_vkeys[l] = nullptr; dev_tris[l] = nullptr;
-    if (!fields[l]) return pa_fail(ctx, "pa_mc_hierarchy_xyz: null state");
-    if (fields[l]->lev->domhi[2] == fields[l]->lev->domlo[2]) return pa_fail(ctx, "pa_mc_hierarchy_xyz: 3-D levels only (marching squares keep their coordinate components)");
-    if (l > 0)  // the coarse cell centre needs the coarse level's geometry: level l must be the `ratio` refinement of level l - 1
+    if (!states[l]) return pa_fail(ctx, name + ": null state");
+    const pa_level* L = states[l]->lev;
+    if (xyz && L->domhi[2] == L->domlo[2]) return pa_fail(ctx, name + ": 3-D levels only (marching squares keep their coordinate components)");
+    const pa_level* crse = (xyz && l > 0) ? states[l - 1]->lev : nullptr;
+    if (crse)  // the coarse cell centre needs the coarse level's geometry: level l must be the `ratio` refinement of level l - 1
       for (int d = 0; d < 3; ++d)
-        if ((long long)(fields[l]->lev->domhi[d] - fields[l]->lev->domlo[d] + 1) != (long long)ratio * (fields[l - 1]->lev->domhi[d] - fields[l - 1]->lev->domlo[d] + 1) ||
-            fields[l]->lev->domlo[d] != ratio * fields[l - 1]->lev->domlo[d])
-          return pa_fail(ctx, "pa_mc_hierarchy_xyz: level " + std::to_string(l) + " is not the ratio-" + std::to_string(ratio) + " refinement of level " + std::to_string(l - 1));
-    const pa_level* fine = (fine_mask && fine_mask[l] && l + 1 < nlev) ? fields[l + 1]->lev : nullptr;
-    if (mc_prepare(ctx, fields[l], fields[l], 0, loops[l], isocomp, isoval, nvert[l], ntri[l], 0, 1, fine, ratio, W[l], l > 0 ? fields[l - 1]->lev : nullptr, 1, ratio)) return 1;
-  }
-  if (mc_run(ctx, nlev, W.data())) return 1;
-  for (int l = 0; l < nlev; ++l) {
-    dev_verts[l] = W[l].dv; dev_vkeys[l] = W[l].dk; dev_tris[l] = W[l].dt;
-    if (W[l].dv && !*block) *block = W[l].dv;
-  }
-  return 0;
-}
-
-extern "C" int pa_mc_hierarchy_fine(pa_ctx* ctx, int nlev, const pa_mf* const* states, const int32_t* fine_mask, int ratio, const pa_box* const* loops, int isocomp,
-                                    double isoval, int64_t* const* nvert, int64_t* const* ntri, double** dev_verts, int32_t** dev_vkeys, int32_t** dev_tris, void** block) {
-  PaBind bind_(ctx);
-  if (!ctx || nlev <= 0 || !states || !loops || !nvert || !ntri || !dev_verts || !dev_vkeys || !dev_tris || !block) return pa_fail(ctx, "pa_mc_hierarchy_fine: null argument");
-  if (ratio < 1) return pa_fail(ctx, "pa_mc_hierarchy_fine: bad refinement ratio");
-  *block = nullptr;
-  std::vector<MclWork> W((size_t)nlev);
-  for (int l = 0; l < nlev; ++l) {
-    dev_verts[l] = nullptr; dev_vkeys[l] = nullptr; dev_tris[l] = nullptr;
-    if (!states[l]) return pa_fail(ctx, "pa_mc_hierarchy_fine: null state");
+        if ((long long)(L->domhi[d] - L->domlo[d] + 1) != (long long)ratio * (crse->domhi[d] - crse->domlo[d] + 1) || L->domlo[d] != ratio * crse->domlo[d])
+          return pa_fail(ctx, name + ": level " + std::to_string(l) + " is not the ratio-" + std::to_string(ratio) + " refinement of level " + std::to_string(l - 1));
     const pa_level* fine = (fine_mask && fine_mask[l] && l + 1 < nlev) ? states[l + 1]->lev : nullptr;
-    if (mc_prepare(ctx, states[l], states[l], 0, loops[l], isocomp, isoval, nvert[l], ntri[l], 0, 1, fine, ratio, W[l])) return 1;
+    if (mc_prepare(ctx, states[l], states[l], 0, loops[l], isocomp, isoval, nvert[l], ntri[l], 0, 1, fine, ratio, W[l], crse, xyz, xyz ? ratio : 0)) return 1;
   }
-  if (mc_run(ctx, nlev, W.data())) return 1;
+  if (mc_run(ctx, name.c_str(), nlev, W.data())) return 1;
   for (int l = 0; l < nlev; ++l) {
     dev_verts[l] = W[l].dv; dev_vkeys[l] = W[l].dk; dev_tris[l] = W[l].dt;
     if (W[l].dv && !*block) *block = W[l].dv;  // the first level with a surface starts the block
   }
   return 0;
+}
+extern "C" int pa_mc_hierarchy_fine(pa_ctx* ctx, int nlev, const pa_mf* const* states, const int32_t* fine_mask, int ratio, const pa_box* const* loops, int isocomp,
+                                    double isoval, int64_t* const* nvert, int64_t* const* ntri, double** dev_verts, int32_t** dev_vkeys, int32_t** dev_tris, void** block) {
+  PaBind bind_(ctx);
+  return mc_hierarchy_impl(ctx, "pa_mc_hierarchy_fine", 0, nlev, states, fine_mask, ratio, loops, isocomp, isoval, nvert, ntri, dev_verts, dev_vkeys, dev_tris, block);
+}
+// pa_mc_hierarchy_fine on states WITHOUT coordinate components
+extern "C" int pa_mc_hierarchy_xyz(pa_ctx* ctx, int nlev, const pa_mf* const* fields, const int32_t* fine_mask, int ratio, const pa_box* const* loops, int isocomp,
+                                   double isoval, int64_t* const* nvert, int64_t* const* ntri, double** dev_verts, int32_t** dev_vkeys, int32_t** dev_tris, void** block) {
+  PaBind bind_(ctx);
+  return mc_hierarchy_impl(ctx, "pa_mc_hierarchy_xyz", 1, nlev, fields, fine_mask, ratio, loops, isocomp, isoval, nvert, ntri, dev_verts, dev_vkeys, dev_tris, block);
 }

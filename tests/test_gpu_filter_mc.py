@@ -432,12 +432,46 @@ def test_level_entry_points_reject_bad_arguments(ctx):
         ctx.lib.pa_device_free(ctx.h, pv)
 
 
-@pytest.mark.parametrize("name,ng", [("amr3_wall_z", 1), ("amr2_allwalls_ragged", 2), ("amr3_sym_x", 1), ("amr5_wall_z", 1)])  # 5 levels: level by level inside the call
-def test_marching_cubes_hierarchy_call_matches_oracle_and_level_calls(ctx, oracle, name, ng):
+def _mc_hierarchy_raw(ctx, states, fine_mask, loops_per_level, isocomp, isoval, ratio=2):
+    """pa_mc_hierarchy_fine without the download: (block, bytes of the block as the header lays it out, per-level pointers
+    (verts, keys, tris) as integers or None, per-level totals (nv, nt)); the caller frees the block"""
+    nlev = len(states)
+    arrs, nvs, nts = [], [], []
+    for lp in loops_per_level:
+        arr = (capi.PaBox * max(len(lp), 1))()
+        for b in range(len(lp)):
+            for d in range(3):
+                arr[b].lo[d], arr[b].hi[d] = int(lp[b, d]), int(lp[b, 3 + d])
+        arrs.append(arr)
+        nvs.append((C.c_int64 * max(len(lp), 1))())
+        nts.append((C.c_int64 * max(len(lp), 1))())
+    parr = (C.POINTER(capi.PaBox) * nlev)(*[C.cast(a, C.POINTER(capi.PaBox)) for a in arrs])
+    pnv = (C.POINTER(C.c_int64) * nlev)(*[C.cast(a, C.POINTER(C.c_int64)) for a in nvs])
+    pnt = (C.POINTER(C.c_int64) * nlev)(*[C.cast(a, C.POINTER(C.c_int64)) for a in nts])
+    fm = (C.c_int32 * nlev)(*[int(bool(f)) for f in fine_mask])
+    pv, pk, pt = (C.c_void_p * nlev)(), (C.c_void_p * nlev)(), (C.c_void_p * nlev)()
+    block = C.c_void_p()
+    ctx.check(ctx.lib.pa_mc_hierarchy_fine(ctx.h, nlev, (C.c_void_p * nlev)(*[m.h for m in states]), fm, int(ratio), parr, int(isocomp), float(isoval),
+                                           pnv, pnt, pv, pk, pt, C.byref(block)))
+    tot = [(int(sum(nvs[l][:len(lp)])), int(sum(nts[l][:len(lp)]))) for l, lp in enumerate(loops_per_level)]
+    al = lambda n: (n + 255) // 256 * 256  # vertices | keys | triangles of a level, each 256-byte aligned
+    nbytes = sum(al(nv * states[l].ncomp * 8) + al(nv * 24) + al(max(8, nt * 12)) for l, (nv, nt) in enumerate(tot) if nv or nt)
+    return block, nbytes, [(pv[l], pk[l], pt[l]) for l in range(nlev)], tot
+
+
+@pytest.mark.parametrize("name,ng,cells", [pytest.param("amr3_wall_z", 1, "slab", id="amr3_wall_z-1"), pytest.param("amr2_allwalls_ragged", 2, "slab", id="amr2_allwalls_ragged-2"),
+                                           pytest.param("amr3_sym_x", 1, "slab", id="amr3_sym_x-1"),
+                                           pytest.param("amr5_wall_z", 1, "slab", id="amr5_wall_z-1"),  # 5 levels: two chunks of launches inside the call
+                                           pytest.param("amr3_wall_z", 1, "tiles", id="amr3_wall_z-1-fallbacks")])
+def test_marching_cubes_hierarchy_call_matches_oracle_and_level_calls(ctx, oracle, name, ng, cells, options):
     """pa_mc_hierarchy_fine (all levels in one call: one count read-back, one pooled output block) against the oracle's per-FAB
-    Polygonise loop and against pa_mc_level_fine level by level -- vertices bit for bit, keys and connectivity identical; a
-    level whose loop boxes are all empty, and a second call that reuses the cached block"""
+    Polygonise loop and against pa_mc_level_fine, one call per level -- vertices bit for bit, keys and connectivity identical; the
+    same with every level on the first form of the cell pass (PA_FORCE_FALLBACKS=1); a level whose loop boxes are all empty (the
+    finest one, and the middle one of three); a second call that reuses the cached block; five levels (more than one launch
+    holds) in ONE block"""
     from util import build_config, make_states
+    if cells == "tiles":
+        options(PA_FORCE_FALLBACKS=1)
     H, per, sym, fn = build_config(name)
     fields = make_states(H, 2, 0, fn, seed=12)
     nc = 5
@@ -487,6 +521,47 @@ def test_marching_cubes_hierarchy_call_matches_oracle_and_level_calls(ctx, oracl
     off[-1][:, 3] = off[-1][:, 0] - 1
     got = capi.mc_hierarchy(ctx, dst, fm, off, 3, iso)
     assert all(len(t) == 0 for (_, _, t) in got[-1]) and sum(len(t) for lev in got[:-1] for (_, _, t) in lev) > 0
+    if H.nlev == 3:  # a MIDDLE level without work: null parts for it, levels 0 and 2 as the oracle has them
+        off = [lp.copy() for lp in loops]
+        off[1][:, 3] = off[1][:, 0] - 1
+        block, _, ptrs, tot = _mc_hierarchy_raw(ctx, dst, fm, off, 3, iso)
+        try:
+            assert ptrs[1] == (None, None, None) and tot[1] == (0, 0)
+            assert all(p is not None for l in (0, 2) for p in ptrs[l]) and tot[0][1] > 0 and tot[2][1] > 0
+        finally:
+            ctx.lib.pa_device_free(ctx.h, block)
+        got = capi.mc_hierarchy(ctx, dst, fm, off, 3, iso)
+        assert all(len(v) == 0 and len(t) == 0 for (v, _, t) in got[1])
+        for l in (0, 2):
+            for b in range(H.levels[l].nboxes):
+                (v, k, t), (gv, gk, gt) = want[l][b], got[l][b]
+                assert np.array_equal(gk, k) and np.array_equal(gt, t), f"{name}, level 1 off: level {l} box {b}: keys / connectivity differ"
+                assert np.array_equal(gv.view(np.int64), np.ascontiguousarray(v).view(np.int64)), f"{name}, level 1 off: level {l} box {b}: vertex data not bit-identical"
+    if H.nlev > 4:  # more levels than one launch holds: still ONE block, and a second call takes it from the cache
+        c5 = capi.Context(0)  # (an empty block cache: which block a call gets does not depend on the tests that ran before)
+        own = []
+        try:
+            dl5 = [capi.DevLevel(c5, lv) for lv in H.levels]
+            own += dl5
+            ds5 = [capi.DevMF.from_host(c5, dl, s) for dl, s in zip(dl5, states)]
+            own += ds5
+            blocks = []
+            for rep in range(2):
+                block, nbytes, ptrs, tot = _mc_hierarchy_raw(c5, ds5, fm, loops, 3, iso)
+                try:
+                    assert block.value and [nt > 0 for (_, nt) in tot] == [any(len(t) for (_, _, t) in wl) for wl in want]
+                    for l, (nv, nt) in enumerate(tot):
+                        assert (ptrs[l][0] is not None) == (nv > 0 or nt > 0)
+                        for p, n in zip(ptrs[l], (nv * nc * 8, nv * 24, nt * 12)):
+                            assert p is None or (block.value <= p and p + n <= block.value + nbytes), f"level {l}: part outside the block"
+                    blocks.append(block.value)
+                finally:
+                    c5.lib.pa_device_free(c5.h, block)
+            assert blocks[0] == blocks[1], "the second call did not reuse the cached block"
+        finally:
+            for m in reversed(own):  # multifabs before their levels
+                m.close()
+            c5.close()
     got = capi.mc_hierarchy(ctx, dst, fm, loops, 3, 1.0e30)
     assert all(len(t) == 0 and len(v) == 0 for lev in got for (v, _, t) in lev)
 
@@ -537,7 +612,7 @@ def test_fillpatch_two_levels_refinement_ratio_4(ctx, oracle, interp, ng):
 
 
 def test_marching_cubes_refinement_ratio_4(ctx, oracle):
-    """the fine-covered mask with the finer level coarsened by 4 (isosurface.cpp:1543) evaluated in the cell pass -- level by
+    """the fine-covered mask with the finer level coarsened by 4 (isosurface.cpp:1543) evaluated in the cell pass -- one call per
     level and through pa_mc_hierarchy_fine -- and the mask multifab form, against the oracle's per-FAB loop"""
     from util import make_states, field_flame
     H = _ratio4_hierarchy((0, 0, 0))
@@ -616,6 +691,62 @@ def test_marching_cubes_refinement_ratio_4(ctx, oracle):
         got.append(lev)
     check(got, "pa_mc_level_fine ratio 4")
     check(capi.mc_hierarchy(ctx, dst, [1, 0], loops, 3, iso, ratio=4), "pa_mc_hierarchy_fine ratio 4")
+
+
+def test_marching_cubes_hierarchy_with_a_level_too_wide_for_the_slab_cell_pass(ctx, oracle):
+    """one call, two forms of the cell pass: level 0 is one box of 824 x 8 x 8 cells -- 826 with its ghost layer, more than the
+    819 the slab form holds, so it takes the first form (k_mcl_cells<8>) with no switch set -- and level 1 (coarse cells
+    [400, 407] x [2, 5] x [2, 5] refined by 2, two boxes) the slab form inside k_mclb_cells4.  Against the oracle's per-FAB
+    Polygonise loop (vertices bit for bit, keys and connectivity equal) and against one pa_mc_level_fine call per level."""
+    from peleanalysis_amd.hierarchy import Hierarchy, Level, chop_box
+    per, plo, phi = (0, 0, 0), np.zeros(3), np.array([824.0, 8.0, 8.0])
+    l0 = Level(np.array([[0, 0, 0, 823, 7, 7]], np.int32), (0, 0, 0), (823, 7, 7), per, plo, phi)
+    l1 = Level(chop_box((800, 4, 4), (815, 11, 11), 8), (0, 0, 0), (1647, 15, 15), per, plo, phi)
+    H = Hierarchy([l0, l1], 2)
+    assert l1.nboxes == 2
+    ng, nc = 1, 4
+    states = []
+    for l, lv in enumerate(H.levels):
+        st = MultiFab(lv, nc, ng, fill=-666.0)
+        for b in range(lv.nboxes):
+            f = st.fab(b)
+            lo = lv.boxes[b, :3] - ng
+            nz, ny, nx = f.shape[1:]
+            f[0] = ((np.arange(lo[0], lo[0] + nx) + 0.5) * lv.dx[0] + lv.prob_lo[0])[None, None, :]
+            f[1] = ((np.arange(lo[1], lo[1] + ny) + 0.5) * lv.dx[1] + lv.prob_lo[1])[None, :, None]
+            f[2] = ((np.arange(lo[2], lo[2] + nz) + 0.5) * lv.dx[2] + lv.prob_lo[2])[:, None, None]
+            f[3] = f[2] + 0.9 * np.sin(0.21 * f[0]) + 0.35 * np.cos(0.8 * f[1])  # a wavy sheet around z = 4 along the whole box, through the fine patch
+        oracle.fill_boundary(st, 0, nc, ng)
+        if l > 0:
+            assert oracle.lib().orc_fillpatch_two_levels(C.byref(oracle._mf(st)), C.byref(oracle._mf(states[l - 1])), 0, nc, ng, 2, 0) == 0
+        states.append(st)
+    iso = 4.05
+    dls = [capi.DevLevel(ctx, lv) for lv in H.levels]
+    dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, states)]
+    loops, want = [], []
+    for l, lv in enumerate(H.levels):
+        lp, wl = np.zeros((lv.nboxes, 6), np.int64), []
+        for b in range(lv.nboxes):
+            lo, hi, mask, llo, lhi = oracle.iso_fab_inputs(H.levels, states, l, b, ng)
+            lp[b, :3], lp[b, 3:] = llo, lhi
+            wl.append(oracle.mc_fab(np.ascontiguousarray(states[l].fab(b)), mask, lo, hi, 3, iso, llo, lhi))
+        loops.append(lp)
+        want.append(wl)
+    got = capi.mc_hierarchy(ctx, dst, [1, 0], loops, 3, iso)
+    ntri = [0, 0]
+    for l, lv in enumerate(H.levels):
+        lev = capi.mc_level(ctx, dst[l], dls[l + 1] if l + 1 < H.nlev else None, loops[l], 3, iso)
+        for b in range(lv.nboxes):
+            (v, k, t), (gv, gk, gt), (lv_, lk, lt) = want[l][b], got[l][b], lev[b]
+            assert (len(gv), len(gt)) == (len(v), len(t)), f"level {l} box {b}: counts differ"
+            assert np.array_equal(gk, k) and np.array_equal(gt, t), f"level {l} box {b}: keys / connectivity differ"
+            assert np.array_equal(gv.view(np.int64), np.ascontiguousarray(v).view(np.int64)), f"level {l} box {b}: vertex data not bit-identical"
+            assert np.array_equal(gv.view(np.int64), lv_.view(np.int64)) and np.array_equal(gk, lk) and np.array_equal(gt, lt), "hierarchy call != level call"
+            ntri[l] += len(t)
+    assert sum(ntri) > 100 and ntri[0] > 0 and ntri[1] > 0
+    # the sheet is cut by the coarse-fine edge: level 0 has triangles next to the fine patch on both sides and none under it
+    tx, ty = (np.concatenate([v[:, d] for (v, _, _) in want[0]]) for d in (0, 1))
+    assert (tx < 400).any() and (tx > 408).any() and not ((tx > 401.5) & (tx < 406.5) & (ty > 2.6) & (ty < 5.4)).any()
 
 
 @pytest.mark.parametrize("parent", ["1", "0"])

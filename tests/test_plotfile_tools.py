@@ -464,8 +464,8 @@ def test_isosurface_tool_end_to_end(tmp_path, oracle):
 
 @pytest.mark.gpu
 def test_tools_on_a_five_level_plotfile(tmp_path, oracle):
-    """more levels than one batched launch of the library takes (PA_MAXB = 4: the all-levels launches go in chunks, marching cubes level
-    by level): grad3d, curvature3d and isosurface3d against the oracle, bit for bit"""
+    """more levels than one batched launch of the library takes (PA_MAXB = 4: the all-levels launches, those of marching cubes
+    included, go in chunks): grad3d, curvature3d and isosurface3d against the oracle, bit for bit"""
     p, H, mfs = _synth(tmp_path, nlev=5, base=16, box=8, per=(1, 1, 0))
     same = lambda a, c: np.array_equal(np.ascontiguousarray(a).view(np.int64), np.ascontiguousarray(c).view(np.int64))
     _run("grad3d.ex", ["infile=" + p, "gradVar=temp", "is_per=1 1 0"], tmp_path)
