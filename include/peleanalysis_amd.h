@@ -585,6 +585,40 @@ int64_t pa_integral_slots(const pa_integral*);
 int pa_integral_read(pa_ctx*, const pa_integral*, double* out);
 void pa_integral_destroy(pa_integral*);
 
+/* ------------------------------------------------------------- surface PDFs (binMEF.cpp)
+ * The area-weighted PDF (one binned component) or joint PDF (up to 4) of node fields over a triangulated surface.  Every triangle is
+ * clipped against the bin edges of each binned component (processTriangle, binMEF.cpp:231-331); each piece adds its area to the bin
+ * it lies in.  The pieces are the reference's, operation for operation; the sums are 192-bit fixed-point integers scaled from the
+ * largest element area and rounded once at read: the same bits for every order of the elements, every list capacity and with
+ * uncombined.  An element with a value that is not finite in x, y, z, a binned component or (condApply) the condition component is
+ * skipped and counted.  A split fraction outside [0, 1] (the reference's AMREX_ALWAYS_ASSERT, :121 / :159) makes read fail.
+ * One GPU.  All arrays are HOST memory; add_surface uploads what it needs and returns when the surface has been binned. */
+typedef struct pa_surfbin pa_surfbin;
+/* binMEF.cpp:417-458, :477-489: nc <= 4 binned components with nbins[j] bins over [bin_min[j], bin_max[j]]; at most 2^24 bins in all.
+ * work_items: the capacity of the work list in triangles (248 bytes each, two lists); 0 = the default (2^19).  A small value forces the
+ * list to be worked off in slices (same bits).  4 R^2 / 3 with R = the sum of nbins[j] + 3 suffices (in exact arithmetic; DESIGN.md 3.9 names the rounding
+ * case the proof leaves open); a smaller list works while the triangles span few bins, and add_surface fails with a message, never
+ * with a write out of bounds, only when the children of one work item do not fit. */
+pa_surfbin* pa_surfbin_create(pa_ctx*, int nc, const int32_t* nbins, const double* bin_min, const double* bin_max, int64_t work_items);
+/* zero the table and fix the scale: area_max >= the area of every element that will be added until read (pa_surfbin_max_area of
+ * each surface, the largest).  The scale cannot change once a sum has begun and a table may take several surfaces, so the CALLER
+ * computes the magnitude and passes it here; add_surface does not.  A larger area sets the overflow flag, and read fails. */
+int pa_surfbin_begin(pa_ctx*, pa_surfbin*, double area_max);
+/* triangleArea (binMEF.cpp:46-60) of every element, the largest finite one; -1 when an element names a node outside 1 .. nnodes */
+double pa_surfbin_max_area(int64_t nnodes, const double* x, const double* y, const double* z, int64_t nelts, const int32_t* elts);
+/* the element loop (binMEF.cpp:522-540): comps[j] = the node values [nnodes] of binned component j, cond = those of condComp (NULL
+ * without cond_apply), elts = [nelts][3] node numbers, 1-based.  cond_apply / cond_sgn / cond_val: :206-226, :465-475; area_eps: :244, :504.
+ * uncombined != 0: one set of global atomics per leaf (measurement; identical bits). */
+int pa_surfbin_add_surface(pa_ctx*, pa_surfbin*, int64_t nnodes, const double* x, const double* y, const double* z, const double* const* comps,
+                           const double* cond, int64_t nelts, const int32_t* elts, int cond_apply, int cond_sgn, double cond_val, double area_eps,
+                           int uncombined);
+/* the table the output of binMEF.cpp:594-670 is made from: area, hits [prod nbins], first component slowest (the order of the
+ * reference's map); a bin is nonempty when hits > 0.  total_area: the sum of :535; outside_area: areaOutsideCondition (:265).
+ * counters [8] (may be NULL): NmyTriangles (:257), skipped elements, rounds, peak list occupancy, sliced rounds, work items walked,
+ * elements, list capacity. */
+int pa_surfbin_read(pa_ctx*, const pa_surfbin*, double* area, int64_t* hits, double* total_area, double* outside_area, int64_t* counters);
+void pa_surfbin_destroy(pa_surfbin*);
+
 /* ------------------------------------------------------------- stream tubes (streamTubeStats.cpp)
  * The three lines through the nodes of a surface triangle bound a stream tube; between consecutive line points it is a wedge.
  * DATA LAYOUT: the Str FABs of a streamSampleFile, all levels and boxes back to back (box g after the boxes before it): a buffer of

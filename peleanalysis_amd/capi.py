@@ -206,6 +206,12 @@ def load_library() -> C.CDLL:
         "pa_integral_slots": (i64, [vp]),
         "pa_integral_read": (C.c_int, [vp, vp, pdbl]),
         "pa_integral_destroy": (None, [vp]),
+        "pa_surfbin_create": (vp, [vp, C.c_int, pi32, pdbl, pdbl, i64]),
+        "pa_surfbin_begin": (C.c_int, [vp, vp, dbl]),
+        "pa_surfbin_max_area": (dbl, [i64, pdbl, pdbl, pdbl, i64, pi32]),
+        "pa_surfbin_add_surface": (C.c_int, [vp, vp, i64, pdbl, pdbl, pdbl, C.POINTER(pdbl), pdbl, i64, pi32, C.c_int, C.c_int, dbl, dbl, C.c_int]),
+        "pa_surfbin_read": (C.c_int, [vp, vp, pdbl, C.POINTER(i64), pdbl, pdbl, C.POINTER(i64)]),
+        "pa_surfbin_destroy": (None, [vp]),
         "pa_tube_create": (vp, [vp, i32, C.POINTER(i64), i64, pi32, i64, pi32]),
         "pa_tube_destroy": (None, [vp]),
         "pa_tube_wedges": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
@@ -1096,3 +1102,75 @@ class IntegralAcc:
         out = np.zeros((self.nrows,) + self.shape)
         self.ctx.check(self.ctx.lib.pa_integral_read(self.ctx.h, self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
+
+
+class SurfBin:
+    """the area-weighted (joint) PDF of node fields over a triangulated surface (binMEF.cpp; pa_surfbin_*): up to 4 binned components,
+    the table in the order of the reference's map (first component slowest)"""
+
+    COUNTERS = ("n_my", "nonfinite", "rounds", "peak", "sliced", "items", "elements", "capacity")
+
+    def __init__(self, ctx: Context, nbins, bin_min, bin_max, work_items: int = 0):
+        self.ctx = ctx
+        self.nbins = tuple(int(n) for n in nbins)
+        self.nc = len(self.nbins)
+        assert len(bin_min) == self.nc and len(bin_max) == self.nc
+        nb = (C.c_int32 * self.nc)(*self.nbins)
+        mn = (C.c_double * self.nc)(*[float(v) for v in bin_min])
+        mx = (C.c_double * self.nc)(*[float(v) for v in bin_max])
+        self.h = ctx.lib.pa_surfbin_create(ctx.h, self.nc, nb, mn, mx, int(work_items))
+        if not self.h:
+            raise PaError(ctx.lib.pa_last_error(ctx.h).decode())
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.pa_surfbin_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @staticmethod
+    def _cols(nodes, elts):
+        nodes = np.asarray(nodes, dtype=np.float64)
+        cols = [np.ascontiguousarray(nodes[:, c]) for c in range(nodes.shape[1])]
+        return cols, np.ascontiguousarray(elts, dtype=np.int32).reshape(-1, 3)
+
+    def max_area(self, nodes, elts) -> float:
+        """the largest finite element area: the magnitude for begin"""
+        cols, e = self._cols(nodes, elts)
+        pd = C.POINTER(C.c_double)
+        a = self.ctx.lib.pa_surfbin_max_area(len(cols[0]), cols[0].ctypes.data_as(pd), cols[1].ctypes.data_as(pd), cols[2].ctypes.data_as(pd), len(e),
+                                             e.ctypes.data_as(C.POINTER(C.c_int32)))
+        if a < 0:
+            raise PaError("pa_surfbin_max_area: an element names a node that does not exist")
+        return a
+
+    def begin(self, area_max: float):
+        self.ctx.check(self.ctx.lib.pa_surfbin_begin(self.ctx.h, self.h, float(area_max)))
+
+    def add_surface(self, nodes, elts, bin_comps, cond_apply: bool = False, cond_comp: int = 0, cond_val: float = 0.0, cond_sgn: int = 0,
+                    area_eps: float = 1.0e-20, uncombined: bool = False):
+        """nodes [N][nComp] with x, y, z first; elts [M][3], 1-based; bin_comps: the node component of every binned component"""
+        assert len(bin_comps) == self.nc
+        cols, e = self._cols(nodes, elts)
+        pd = C.POINTER(C.c_double)
+        comps = (pd * self.nc)(*[cols[int(c)].ctypes.data_as(pd) for c in bin_comps])
+        cond = cols[int(cond_comp)].ctypes.data_as(pd) if cond_apply else None
+        self.ctx.check(self.ctx.lib.pa_surfbin_add_surface(self.ctx.h, self.h, len(cols[0]), cols[0].ctypes.data_as(pd), cols[1].ctypes.data_as(pd),
+                                                           cols[2].ctypes.data_as(pd), comps, cond, len(e), e.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                           int(bool(cond_apply)), int(cond_sgn), float(cond_val), float(area_eps), int(bool(uncombined))))
+
+    def read(self):
+        """(area [prod nbins], hits [prod nbins], total area, area outside the condition, counters by name)"""
+        nt = int(np.prod(self.nbins, dtype=np.int64))
+        area, hits = np.zeros(nt), np.zeros(nt, dtype=np.int64)
+        tot, outside = C.c_double(0.0), C.c_double(0.0)
+        cnt = np.zeros(8, dtype=np.int64)
+        p64 = C.POINTER(C.c_int64)
+        self.ctx.check(self.ctx.lib.pa_surfbin_read(self.ctx.h, self.h, area.ctypes.data_as(C.POINTER(C.c_double)), hits.ctypes.data_as(p64), C.byref(tot),
+                                                    C.byref(outside), cnt.ctypes.data_as(p64)))
+        return area, hits, tot.value, outside.value, dict(zip(self.COUNTERS, (int(v) for v in cnt)))

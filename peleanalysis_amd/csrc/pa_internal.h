@@ -357,6 +357,9 @@ int pa_gradcurv_fix_levels(pa_ctx* ctx, int nlev, pa_mf* const* phi, int pcomp, 
 // pa_fused_irreg.hip
 bool pa_fused2_level_ok(const pa_level* L);
 int pa_gauss_cells_levels(pa_ctx* ctx, int nlev, pa_mf* const* G, pa_mf* const* out, int pc, int kgc, double thr);
+// pa_binmef.hip
+std::vector<double> pa_binmef_edges(double bmin, double bmax, int n);
+long long pa_binmef_slice(const int* cr, long long n, long long cap, long long* tot);
 
 // The current HIP device is per host thread, and a pa_ctx may be used from a thread other than the one that created it
 // (tools bring the context up on a worker thread) or next to contexts of other devices (ngpus > 1 in one process):
