@@ -619,6 +619,34 @@ int pa_surfbin_add_surface(pa_ctx*, pa_surfbin*, int64_t nnodes, const double* x
 int pa_surfbin_read(pa_ctx*, const pa_surfbin*, double* area, int64_t* hits, double* total_area, double* outside_area, int64_t* counters);
 void pa_surfbin_destroy(pa_surfbin*);
 
+/* ------------------------------------------------------------- hex-element mesh of a hierarchy (amrToFE.cpp)
+ * The centres of all uncovered cells of the levels become nodes, every 2 x 2 x 2 block of them an 8-node brick; at a coarse-fine
+ * interface the ghost corners of the fine bricks collapse onto coarse cell centres.  Node ids, element order and connectivity are the
+ * reference's (std::map<Node,int> filled level -> grid -> cell, std::set<Element> in Element::operator< order), built by compaction
+ * and radix sorts; the same input gives the same bytes.  One GPU, 3-D levels, nGrowPer = 0.  The calls are
+ * synchronous except pa_fe_gather, which is asynchronous on the context's stream. */
+typedef struct pa_fe pa_fe;
+/* amrToFE.cpp:374-452 and :465-633.  levels: the file's BoxArrays (up to 8); ratios [nlev - 1]; subbox: the box key in level-0 indices
+ * (NULL: the domain; it is intersected with the domain, and refined level by level); a level no box of which touches its subbox ends the
+ * hierarchy (:445-451; *nlev_used).  connect_cc = 0: one flat brick per node (:603, :626-633, :775-813), nnodes = 8 * nelts.
+ * Fails (NULL, pa_last_error) where the reference misnumbers or writes out of bounds: a fine box that is not aligned to its ratio
+ * (:499-507), a corner that lies in no grid ("Node not found in node map", :615-619), counts beyond int. */
+pa_fe* pa_fe_build(pa_ctx*, int nlev, const pa_level* const* levels, const int32_t* ratios, const pa_box* subbox, int connect_cc,
+                   int32_t* nlev_used, int64_t* nnodes, int64_t* nelts);
+/* amrToFE.cpp:608-633: connData, [nelts][8] node numbers, 1-based, corners in the order of :585-592; a DEVICE array owned by the mesh */
+int pa_fe_connectivity(pa_ctx*, const pa_fe*, const int32_t** dev_conn);
+/* amrToFE.cpp:638-646: nodeVect, (level, i, j, k) of every node id, [*nids][4]; a DEVICE array owned by the mesh.  *nids is the number
+ * of uncovered cells (= nelts without connect_cc) */
+int pa_fe_nodes(pa_ctx*, const pa_fe*, int64_t* nids, const int32_t** dev_nodes);
+/* amrToFE.cpp:711-814: tmpData in block ordering, dev_out [3 + ncomp][nnodes] (device): x, y, z = plo + (iv + 0.5) * dx with dx =
+ * ProbSize / domain length of the node's level (:718-724), then components comps[0 .. ncomp-1] of the node's cell.  mfs[l]: a multifab
+ * on levels[l] of the build (any ghost width), l < nlev_used. */
+int pa_fe_gather(pa_ctx*, pa_fe*, int nlev, const pa_mf* const* mfs, int ncomp, const int32_t* comps, double* dev_out);
+/* HIP-event times in ms of the build's stages -- number, tag, cubes, order -- and of the last gather; ncubes (may be NULL): cubes kept
+ * before duplicate removal (tools/amrtofe_bench.py) */
+int pa_fe_stage_times(pa_ctx*, const pa_fe*, double ms[5], int64_t* ncubes);
+void pa_fe_destroy(pa_fe*);
+
 /* ------------------------------------------------------------- stream tubes (streamTubeStats.cpp)
  * The three lines through the nodes of a surface triangle bound a stream tube; between consecutive line points it is a wedge.
  * DATA LAYOUT: the Str FABs of a streamSampleFile, all levels and boxes back to back (box g after the boxes before it): a buffer of

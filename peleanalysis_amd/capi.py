@@ -212,6 +212,12 @@ def load_library() -> C.CDLL:
         "pa_surfbin_add_surface": (C.c_int, [vp, vp, i64, pdbl, pdbl, pdbl, C.POINTER(pdbl), pdbl, i64, pi32, C.c_int, C.c_int, dbl, dbl, C.c_int]),
         "pa_surfbin_read": (C.c_int, [vp, vp, pdbl, C.POINTER(i64), pdbl, pdbl, C.POINTER(i64)]),
         "pa_surfbin_destroy": (None, [vp]),
+        "pa_fe_build": (vp, [vp, C.c_int, C.POINTER(vp), pi32, C.POINTER(PaBox), C.c_int, pi32, C.POINTER(i64), C.POINTER(i64)]),
+        "pa_fe_connectivity": (C.c_int, [vp, vp, C.POINTER(vp)]),
+        "pa_fe_nodes": (C.c_int, [vp, vp, C.POINTER(i64), C.POINTER(vp)]),
+        "pa_fe_gather": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), C.c_int, pi32, vp]),
+        "pa_fe_stage_times": (C.c_int, [vp, vp, pdbl, C.POINTER(i64)]),
+        "pa_fe_destroy": (None, [vp]),
         "pa_tube_create": (vp, [vp, i32, C.POINTER(i64), i64, pi32, i64, pi32]),
         "pa_tube_destroy": (None, [vp]),
         "pa_tube_wedges": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
@@ -1174,3 +1180,73 @@ class SurfBin:
         self.ctx.check(self.ctx.lib.pa_surfbin_read(self.ctx.h, self.h, area.ctypes.data_as(C.POINTER(C.c_double)), hits.ctypes.data_as(p64), C.byref(tot),
                                                     C.byref(outside), cnt.ctypes.data_as(p64)))
         return area, hits, tot.value, outside.value, dict(zip(self.COUNTERS, (int(v) for v in cnt)))
+
+
+class FeMesh:
+    """the hex-element mesh of a hierarchy (amrToFE.cpp; pa_fe_*): nodes = the uncovered cells in the reference's id order, bricks in
+    the order of its std::set<Element>.  levels: DevLevel per level on the FILE's boxes; ratios: one per level but the finest;
+    subbox: (lo0, lo1, lo2, hi0, hi1, hi2) on level 0 or None; finest_level: as the tool's key"""
+
+    STAGES = ("number", "tag", "cubes", "order", "gather")
+
+    def __init__(self, ctx: Context, levels: Sequence["DevLevel"], ratios: Sequence[int], subbox=None, finest_level: Optional[int] = None,
+                 connect_cc: bool = True):
+        self.ctx = ctx
+        levels = list(levels if finest_level is None else levels[:finest_level + 1])
+        nlev = len(levels)
+        hs = (C.c_void_p * nlev)(*[lv.h for lv in levels])
+        rr = (C.c_int32 * max(nlev - 1, 1))(*[int(r) for r in list(ratios)[:nlev - 1]])
+        bx = None
+        if subbox is not None:
+            bx = PaBox()
+            for d in range(3):
+                bx.lo[d], bx.hi[d] = int(subbox[d]), int(subbox[3 + d])
+        used, nn, ne = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self.h = ctx.lib.pa_fe_build(ctx.h, nlev, hs, rr, C.byref(bx) if bx is not None else None, int(bool(connect_cc)), C.byref(used), C.byref(nn), C.byref(ne))
+        if not self.h:
+            raise PaError(ctx.lib.pa_last_error(ctx.h).decode())
+        self.nlev, self.nnodes, self.nelts = used.value, nn.value, ne.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.pa_fe_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def connectivity(self) -> np.ndarray:
+        """int32 [nelts][8], 1-based"""
+        p = C.c_void_p()
+        self.ctx.check(self.ctx.lib.pa_fe_connectivity(self.ctx.h, self.h, C.byref(p)))
+        out = np.empty((self.nelts, 8), dtype=np.int32)
+        if self.nelts:
+            self.ctx.check(self.ctx.lib.pa_memcpy_d2h(self.ctx.h, out.ctypes.data_as(C.c_void_p), p, out.nbytes))
+        return out
+
+    def nodes(self) -> np.ndarray:
+        """int32 [ids][4]: (level, i, j, k) of every node id"""
+        p, n = C.c_void_p(), C.c_int64(0)
+        self.ctx.check(self.ctx.lib.pa_fe_nodes(self.ctx.h, self.h, C.byref(n), C.byref(p)))
+        out = np.empty((n.value, 4), dtype=np.int32)
+        self.ctx.check(self.ctx.lib.pa_memcpy_d2h(self.ctx.h, out.ctypes.data_as(C.c_void_p), p, out.nbytes))
+        return out
+
+    def gather(self, mfs: Sequence["DevMF"], comps: Sequence[int], download: bool = True):
+        """float64 [3 + len(comps)][nnodes]: x, y, z, then the components (download=False: the DevBuf)"""
+        comps = [int(c) for c in comps]
+        buf = DevBuf(self.ctx, 8 * (3 + len(comps)) * max(self.nnodes, 1))
+        cc = (C.c_int32 * max(len(comps), 1))(*comps)
+        self.ctx.check(self.ctx.lib.pa_fe_gather(self.ctx.h, self.h, len(mfs), _handles(mfs), len(comps), cc, C.c_void_p(buf.ptr)))
+        if not download:
+            return buf
+        return buf.to_numpy(np.float64, (3 + len(comps), self.nnodes))
+
+    def stage_times(self):
+        """({stage: ms}, cubes kept before duplicate removal)"""
+        ms, nc = (C.c_double * 5)(), C.c_int64(0)
+        self.ctx.check(self.ctx.lib.pa_fe_stage_times(self.ctx.h, self.h, ms, C.byref(nc)))
+        return dict(zip(self.STAGES, (float(v) for v in ms))), nc.value

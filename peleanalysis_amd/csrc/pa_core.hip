@@ -13,6 +13,18 @@ int pa_fail(pa_ctx* ctx, const std::string& msg) {
   return 1;
 }
 
+int pa_ensure_scr(pa_ctx* ctx, size_t bytes, int slot) {
+  void*& p = slot ? ctx->d_scr2 : ctx->d_scr;
+  size_t& cap = slot ? ctx->scr2_cap : ctx->scr_cap;
+  if (cap >= bytes) return 0;
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  PA_HIP(hipMalloc(&p, bytes));
+  cap = bytes;
+  return 0;
+}
+
 extern "C" int pa_version(void) { return 100; }
 
 // Workgroup table of a sweep (MarchArgs::wgtab, GradMarchArgs::wgtab), cached on the level per box class (0: wider than 32
@@ -267,6 +279,7 @@ extern "C" void pa_ctx_destroy(pa_ctx* ctx) {
   for (hipEvent_t e : ctx->fix_evs)
     if (e) (void)hipEventDestroy(e);
   if (ctx->d_scr) (void)hipFree(ctx->d_scr);
+  if (ctx->d_scr2) (void)hipFree(ctx->d_scr2);
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (ctx->d_mcz) (void)hipFree(ctx->d_mcz);
   for (auto& c : ctx->surf_cache) (void)hipFree(c.first);

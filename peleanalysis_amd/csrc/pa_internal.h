@@ -130,8 +130,10 @@ struct pa_ctx {
   void* d_slow = nullptr;   // cells the clip-aware curvature fix-up hands to its general path (pa_fused_fix.hip: SlowList)
   hipEvent_t fix_evs[2] = {nullptr, nullptr};  // fix-up: perimeter kernel on the side stream (pa_fused_fix.hip)
   double* d_prog = nullptr; // (pmin, 1 / (pmax - pmin)) of the component slots of a batch (pa_gradcurv_run_comps2)
-  void* d_scr = nullptr;    // grow-only scratch (marching cubes)
+  void* d_scr = nullptr;    // grow-only scratch (marching cubes, distance function, hex-element mesh): pa_ensure_scr
   size_t scr_cap = 0;
+  void* d_scr2 = nullptr;   // a second one for work that is sized while the first is in use (pa_amrtofe.hip: the sort's arrays)
+  size_t scr2_cap = 0;
   void* h_pin = nullptr;    // grow-only pinned host buffer (count read-backs of marching cubes)
   size_t h_pin_cap = 0;
   void* d_mcz = nullptr;    // per-cell code bytes of the level-batched marching cubes: all zeros between calls (pa_mc.hip)
@@ -323,6 +325,8 @@ int pa_fail(pa_ctx* ctx, const std::string& msg);
 // header, so the compiler compares declaration and definition; default arguments live here only.
 // pa_core.hip
 int pa_ensure_red(pa_ctx* ctx, size_t n);
+// the context's grow-only scratch holds at least `bytes` afterwards (contents lost when it grows); slot 0: d_scr, 1: d_scr2
+int pa_ensure_scr(pa_ctx* ctx, size_t bytes, int slot = 0);
 int pa_fill_boundary_impl(pa_ctx* ctx, pa_mf* M, int comp, int ncomp, int ng, int no_exchange);
 int pa_fill_boundary_local_batch(pa_ctx* ctx, int n, pa_mf* const* Ms, int comp, int ncomp, int ng);
 int pa_fill_boundary_local_batch_ngs(pa_ctx* ctx, int n, pa_mf* const* Ms, int comp, int ncomp, const int* ngs);

@@ -258,15 +258,7 @@ __global__ __launch_bounds__(256) void k_mc_tris(McGeom G, const unsigned char* 
   }
 }
 
-static int ensure_scr(pa_ctx* ctx, size_t bytes) {
-  if (ctx->scr_cap >= bytes) return 0;
-  if (ctx->d_scr) (void)hipFree(ctx->d_scr);
-  ctx->d_scr = nullptr;
-  ctx->scr_cap = 0;
-  PA_HIP(hipMalloc(&ctx->d_scr, bytes));
-  ctx->scr_cap = bytes;
-  return 0;
-}
+static int ensure_scr(pa_ctx* ctx, size_t bytes) { return pa_ensure_scr(ctx, bytes); }
 
 struct McScratch {
   unsigned char *live, *cidx, *vflag;

@@ -289,15 +289,7 @@ __global__ __launch_bounds__(B == 8 ? 384 : 128) void k_sdf_sweep_blocks(const S
 // cache, sc1 costs 9-30 us).  Bit-identical, but 125-143 ms per 130^3 grid against 76 ms and 15.5 ms per grid in a batch of 16
 // against 8.0: a hyperplane of ~10^4 points is throughput work -- ~18 us on the 32 CUs of one XCD, ~3 on the chip -- so the launch
 // per hyperplane, whose kernel uses all eight XCDs, stays.)
-static int ensure_scr_sdf(pa_ctx* ctx, size_t bytes) {
-  if (ctx->scr_cap >= bytes) return 0;
-  if (ctx->d_scr) (void)hipFree(ctx->d_scr);
-  ctx->d_scr = nullptr;
-  ctx->scr_cap = 0;
-  PA_HIP(hipMalloc(&ctx->d_scr, bytes));
-  ctx->scr_cap = bytes;
-  return 0;
-}
+static int ensure_scr_sdf(pa_ctx* ctx, size_t bytes) { return pa_ensure_scr(ctx, bytes); }
 
 extern "C" int pa_sdf_level_set3(pa_ctx* ctx, int ngrids, const pa_sdf_grid* grids, int exact_band) {
   PaBind bind_(ctx);
