@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import fixed192_ref as F
 import integral_ref as I
 import stats_ref as R
 from peleanalysis_amd import capi
@@ -48,27 +49,40 @@ def _vabs(states, comps, fl):
 
 
 def gpu_integral(ctx, H, states, comps, kind, dir_=0, finest_level=None, ccomp=-1, cmin=0.0, cmax=0.0, squares=False, uncombined=False, vabs=None):
-    """the level loops of integral.cpp:20-44, :79-101, :123-140 on the device -> the raw sums [rows] + shape"""
+    """the level loops of integral.cpp:20-44, :79-101, :123-140 on the device -> the raw sums [rows] + shape, with the magnitudes declared at
+    begin in .declared"""
     fl = H.nlev - 1 if finest_level is None else finest_level
     rr, Rl = R.ref_ratios(H), I.cum_ratios(H, fl)
     w = [I.level_weight(H.levels[l], kind, dir_) for l in range(fl + 1)]
     sub = _sub(states[:fl + 1], comps)
     dls = [capi.DevLevel(ctx, lv) for lv in H.levels[:fl + 1]]
+    vabs = [float(v) for v in (_vabs(states, comps, fl) if vabs is None else vabs)]
     with capi.IntegralAcc(ctx, len(comps), kind, dir_, I.domain_box(H, fl), squares) as acc:
-        acc.begin(max(w), _vabs(states, comps, fl) if vabs is None else vabs)
+        acc.begin(max(w), vabs)
         for l in (range(fl + 1) if kind == 3 else range(fl, -1, -1)):
             with capi.DevMF.from_host(ctx, dls[l], sub[l]) as mf:
                 acc.add_level(mf, dls[l + 1] if l < fl else None, rr[l] if l < fl else 1, Rl[l], w[l], ccomp, cmin, cmax, uncombined=uncombined)
-        out = acc.read()
+        out = acc.read().view(IntegralSums)
     for dl in dls:
         dl.close()
+    out.declared = dict(w_max=max(w), vabs=vabs, squares=squares)
     return out
 
 
-def check_integral(res, got, H, what):
-    """row 0 == the correctly rounded exact sum; rows 1..: the contract's bound in every slot, the IEEE rule where a term is not finite"""
+class IntegralSums(np.ndarray):
+    """the array pa_integral_read fills, with the magnitudes declared at begin in .declared"""
+    declared = None
+
+
+def check_integral(res, got, H, what, bound=True):
+    """row 0 == the correctly rounded exact sum; rows 1..: the contract's bound in every slot AND equal, bit for bit, to the big-integer model at
+    the scales of the declared magnitudes (== fsum where the terms convert exactly); the IEEE rule where a term is not finite.
+    bound=False (tests/test_gpu_fixed_sums.py only): inputs with terms below the quantum 2^(k-157), which the accumulator truncates by design --
+    the model includes that, the bound presumes terms it can hold"""
     assert got.shape == (res["nrows"],) + res["shape"], (what, got.shape)
     ns = res["nslots"]
+    s_w, s_row = F.integral_scales(**got.declared)
+    F.assert_bins_match_model(np.asarray(got[0]), res["keys"], res["terms"][0], s_w, ns, f"{what} measure")
     assert np.array_equal(got[0], I.measure_exact(res, H)), f"{what}: the measure is not the correctly rounded exact sum"
     worst = 0.0
     for r in range(1, res["nrows"]):
@@ -77,7 +91,9 @@ def check_integral(res, got, H, what):
         for s, v in special.items():
             assert (math.isnan(v) and math.isnan(S[s])) or S[s] == v, f"{what} row {r} slot {s}: {S[s]} where IEEE addition gives {v}"
             S[s] = 0.0
-        worst = max(worst, R.assert_sum_bound(S, k, t, ns, f"{what} row {r}"))
+        if bound:
+            worst = max(worst, R.assert_sum_bound(S, k, t, ns, f"{what} row {r}"))
+        F.assert_bins_match_model(S, k, t, s_row[r - 1], ns, f"{what} row {r}")
     return worst
 
 
@@ -141,6 +157,7 @@ def test_squares_rows(ctx, nv):
         assert got[0] == math.fsum(r["terms"][0])
         for q in range(1, 7):
             R.assert_sum_bound(got[q:q + 1], r["keys"], r["terms"][q], 1, f"rmsVel sum {q}")
+            F.assert_bins_match_model(np.asarray(got[q:q + 1]), r["keys"], r["terms"][q], F.integral_scales(**got.declared)[1][q - 1], 1, f"rmsVel sum {q}")
 
 
 def test_nonfinite_terms_follow_ieee_addition(ctx):
@@ -293,7 +310,9 @@ def test_error_paths(ctx):
         acc.add_level(mf1, None, 1, 1, w[1])
         acc.add_level(mf0, dl1, 2, 2, w[0])
         res = I.integrate(H, st, [0, 1, 2], 2, 0)
-        check_integral(res, acc.read(), H, "after a failed read")
+        got = acc.read().view(IntegralSums)
+        got.declared = dict(w_max=w[0], vabs=[3000.0] * 3, squares=False)
+        check_integral(res, got, H, "after a failed read")
     with capi.IntegralAcc(ctx, 1, 3, 0, dom0) as acc:  # finestLevel = 0: level 1 does not belong
         acc.begin(1.0, [3000.0])
         with pytest.raises(capi.PaError, match="is not the domain the accumulator was created for"):

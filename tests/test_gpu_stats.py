@@ -6,6 +6,7 @@ run, for a re-tiled level, for a shuffled box order and for the uncombined kerne
 import numpy as np
 import pytest
 
+import fixed192_ref as F
 import stats_ref as R
 from peleanalysis_amd import capi
 from peleanalysis_amd.hierarchy import Hierarchy, Level, MultiFab, field_flame, nested_hierarchy, regrid_copy, retile_level
@@ -35,14 +36,17 @@ def gpu_minmax(ctx, H, states, comps, fl):
     return mn, mx
 
 
-def gpu_jpdf(ctx, H, states, nload, nbins, vmin, vmax, finest_level=None, uncombined=False, **kw):
-    """the level loop of jpdf.cpp:440-522 on the device -> (bin, binX1, binX2 [npairs][nb][nb], outside [npairs][nlev][4], nan [npairs])"""
+def gpu_jpdf(ctx, H, states, nload, nbins, vmin, vmax, finest_level=None, uncombined=False, vabs=None, **kw):
+    """the level loop of jpdf.cpp:440-522 on the device -> (bin, binX1, binX2 [npairs][nb][nb], outside [npairs][nlev][4], nan [npairs]), with the
+    magnitudes declared at begin in .declared.  vabs: the magnitudes of the loaded variables, default the data's own"""
     fl = H.nlev - 1 if finest_level is None else finest_level
     rr = R.ref_ratios(H)
     stoich = bool(kw.get("do_stoichiometry"))
     nvars = nload + (1 if stoich else 0)
-    mn, mx = gpu_minmax(ctx, H, states, list(range(nload)), fl)
-    vabs = list(np.maximum(np.abs(mn), np.abs(mx))) + ([STOICH_ABS] if stoich else [])
+    if vabs is None:
+        mn, mx = gpu_minmax(ctx, H, states, list(range(nload)), fl)
+        vabs = np.maximum(np.abs(mn), np.abs(mx))
+    vabs = [float(v) for v in vabs] + ([STOICH_ABS] if stoich else [])
     dls = [capi.DevLevel(ctx, lv) for lv in H.levels[:fl + 1]]
     P = capi.jpdf_params(nload, vmin, vmax, uncombined=uncombined, **kw)
     outs, nan = [], np.zeros(nvars * (nvars - 1) // 2, np.int64)
@@ -56,11 +60,17 @@ def gpu_jpdf(ctx, H, states, nload, nbins, vmin, vmax, finest_level=None, uncomb
         b, x1, x2 = acc.read()
     for dl in dls:
         dl.close()
-    return b, x1, x2, np.stack(outs, axis=1), nan
+    got = F.Sums((b, x1, x2, np.stack(outs, axis=1), nan))
+    got.declared = dict(vol_max=_vol(H.levels[0]), vabs=vabs)
+    return got
 
 
-def check_jpdf(res, got, nbins, what):
+def check_jpdf(res, got, nbins, what, bound=True):
+    """the counters and the set of non-empty bins with ==; every bin of every accumulator inside the contract's bound AND equal, bit for bit, to
+    the big-integer model at the scales of the declared magnitudes (tests/fixed192_ref.py), == fsum where the terms convert exactly.  bound=False (tests/test_gpu_fixed_sums.py only): inputs with
+    terms below the quantum 2^(k-157), which the accumulator truncates by design -- the model includes that, the bound presumes terms it can hold"""
     b, x1, x2, outside, nan = got
+    s_vol, s_x = F.jpdf_scales(**got.declared)
     nb2 = nbins * nbins
     assert np.array_equal(outside, res["outside"]), f"{what}: out-of-range counters"
     assert np.array_equal(nan, res["nan"]), f"{what}: NaN counts"
@@ -69,19 +79,25 @@ def check_jpdf(res, got, nbins, what):
         occupied = np.bincount(res["keys"][p], minlength=nb2) > 0
         assert np.array_equal(b[p].ravel() > 0, occupied), f"{what} pair {p}: the set of non-empty bins differs"
         for w, arr in enumerate((b, x1, x2)):
-            worst = max(worst, R.assert_sum_bound(arr[p], res["keys"][p], res["terms"][p][w], nb2, f"{what} pair {p} acc {w}"))
+            if bound:
+                worst = max(worst, R.assert_sum_bound(arr[p], res["keys"][p], res["terms"][p][w], nb2, f"{what} pair {p} acc {w}"))
+            s = s_vol if w == 0 else s_x[res["pairs"][p][w - 1]]
+            F.assert_bins_match_model(arr[p], res["keys"][p], res["terms"][p][w], s, nb2, f"{what} pair {p} acc {w}")
     return worst
 
 
 def gpu_condmean(ctx, H, states, bin_comp, avg_comps, nbins, bin_min, bin_max, finest_level=None, bounds=None, with_minmax=True, uncombined=False,
-                 weights_from=None):
-    """the level loop of conditionalMean.cpp:236-298 on the device -> (hits, sum, sumsq, mn, mx)"""
+                 weights_from=None, vabs=None):
+    """the level loop of conditionalMean.cpp:236-298 on the device -> (hits, sum, sumsq, mn, mx), with the magnitudes declared at begin in
+    .declared.  vabs: the magnitudes of the averaged components, default the data's own"""
     plan = R.condmean_plan(H, finest_level, bounds)
     wplan = plan if weights_from is None else R.condmean_plan(weights_from, finest_level, bounds)
     comps = [bin_comp] + list(avg_comps)
     fl = plan[-1]["level"]
-    mn, mx = gpu_minmax(ctx, H, states, list(avg_comps), fl)
-    vabs = np.maximum(np.abs(mn), np.abs(mx))
+    if vabs is None:
+        mn, mx = gpu_minmax(ctx, H, states, list(avg_comps), fl)
+        vabs = np.maximum(np.abs(mn), np.abs(mx))
+    vabs = [float(v) for v in vabs]
     dls = {P["level"]: capi.DevLevel(ctx, H.levels[P["level"]]) for P in plan}
     with capi.CondMeanAcc(ctx, len(avg_comps), nbins, with_minmax) as acc:
         acc.begin(wplan[0]["weight"], vabs)
@@ -93,19 +109,26 @@ def gpu_condmean(ctx, H, states, bin_comp, avg_comps, nbins, bin_min, bin_max, f
             with capi.DevMF.from_host(ctx, dls[P["level"]], s) as mf:
                 acc.add_level(mf, dls[P["finer"]] if P["finer"] is not None else None, P["ratio"], P["domain"], wplan[q]["weight"], bin_min, bin_max,
                               uncombined=uncombined)
-        out = acc.read()
+        out = F.Sums(acc.read())
     for dl in dls.values():
         dl.close()
+    out.declared = dict(weight_max=wplan[0]["weight"], vabs=vabs)
     return out
 
 
-def check_condmean(res, got, nbins, what):
+def check_condmean(res, got, nbins, what, bound=True):
+    """binHits, minima and maxima with ==; every bin of every sum inside the contract's bound AND equal, bit for bit, to the big-integer model
+    at the scales of the declared magnitudes, == fsum where the terms convert exactly.  bound=False: as for check_jpdf"""
     hits, s, s2, mn, mx = got
+    s_sum, s_sq = F.condmean_scales(**got.declared)
     assert np.array_equal(hits, res["hits"]), f"{what}: binHits"
     worst = 0.0
     for a in range(s.shape[1]):
-        worst = max(worst, R.assert_sum_bound(s[:, a], res["keys"], res["terms_sum"][a], nbins, f"{what} sum {a}"))
-        worst = max(worst, R.assert_sum_bound(s2[:, a], res["keys"], res["terms_sq"][a], nbins, f"{what} sumsq {a}"))
+        if bound:
+            worst = max(worst, R.assert_sum_bound(s[:, a], res["keys"], res["terms_sum"][a], nbins, f"{what} sum {a}"))
+            worst = max(worst, R.assert_sum_bound(s2[:, a], res["keys"], res["terms_sq"][a], nbins, f"{what} sumsq {a}"))
+        F.assert_bins_match_model(s[:, a], res["keys"], res["terms_sum"][a], s_sum[a], nbins, f"{what} sum {a}")
+        F.assert_bins_match_model(s2[:, a], res["keys"], res["terms_sq"][a], s_sq[a], nbins, f"{what} sumsq {a}")
     if mn is not None:
         assert np.array_equal(mn, res["mn"]) and np.array_equal(mx, res["mx"]), f"{what}: per-bin minima / maxima"
     return worst
@@ -169,7 +192,8 @@ def test_jpdf_nan_and_infinite_quotients(ctx):
                 o, n = acc.add_level(mf, dls[l + 1] if l == 0 else None, 2, _vol(H.levels[l]), P)
             outs.append(o)
             nan += n
-        got = acc.read() + (np.stack(outs, axis=1), nan)
+        got = F.Sums(acc.read() + (np.stack(outs, axis=1), nan))
+        got.declared = dict(vol_max=_vol(H.levels[0]), vabs=[1e20, 1e20])
     for dl in dls:
         dl.close()
     check_jpdf(res, got, 16, "NaN / huge values")
