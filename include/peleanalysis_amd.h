@@ -195,7 +195,9 @@ int       pa_level_nboxes(const pa_level*);
  * buffer and its component stride (>= nx*ny*nz incl. ghosts: rounded up to 512 B and kept off
  * multiples of 16 KiB so that the components of one cell do not share an HBM channel); returns
  * the total size in doubles.  Inside a component the layout is the FArrayBox one ([k][j][i]).
- * replaces: MultiFab(ba, dm, ncomp, ngrow) (grad.cpp:164, curvature.cpp:294). */
+ * replaces: MultiFab(ba, dm, ncomp, ngrow) (grad.cpp:164, curvature.cpp:294).
+ * Output contract of every entry point: it stores EVERY valid cell of the components it owns and nothing else -- a caller's devptr
+ * is never cleared, and what a call does not own (ghost cells of an ng = 0 output, components of options that are off) is left as it was. */
 int64_t pa_mf_layout(int nboxes, const int32_t* boxes6, int ncomp, int ng, int64_t* off, int64_t* cstride);
 pa_mf*  pa_mf_create(pa_ctx*, const pa_level*, int ncomp, int ng, double* devptr /* NULL: library allocates */);
 void    pa_mf_destroy(pa_mf*);

@@ -40,7 +40,10 @@ static int host_owner(const pa_level* L, int i, int j, int k);
 // part (round 6, sharded levels): 0 = every tile; 1 = the EARLY tiles, 2 = the rest.  A tile is early when every cell it reads
 // outside its own box -- two cells around the tile, clipped to the FAB -- is a valid cell of a box THIS RANK owns: the local
 // FillBoundary alone completes its input, so its sweep can start while the cross-rank exchange and the ghost preparation that
-// follows it (coarse patches, special faces, ring) are still under way.  Tables of a part list tiles one by one (always built).
+// follows it (coarse patches, special faces, ring) are still under way -- AND it touches no special face of its box: the sweep takes
+// the compact ghost array of a special face for every tile at that face (pa_fused_march3.h: cgxl .. cgzh), also where the part of a
+// partly covered face next to the tile is covered, and those arrays and the ring are written by that chain.  Tables of a part list
+// tiles one by one (always built).
 const WgTab* pa_sweep_wgtab(const pa_level* L, int cls, int tw, int mty, int kseg, bool force, int part) {
   if (part) force = true;
   const long long key = ((long long)cls << 56) | ((long long)part << 54) | ((long long)(force ? 1 : 0) << 52) | ((long long)tw << 40) | ((long long)mty << 24) | (long long)kseg;
@@ -52,6 +55,11 @@ const WgTab* pa_sweep_wgtab(const pa_level* L, int cls, int tw, int mty, int kse
   std::vector<std::vector<int>> sel;    // part != 0: the tiles of bt[i] that belong to the part
   long long real = 0;
   int tmax = 0;
+  std::vector<unsigned char> sp;  // part != 0: special faces of box b, bit 2 * dir + side
+  if (part) {
+    sp.assign(L->boxes.size(), 0);
+    for (int f : L->sfaces) sp[(size_t)(f / 6)] |= (unsigned char)(1u << (f % 6));
+  }
   for (int b = 0; b < (int)L->boxes.size(); ++b) {
     const DBox& B = L->boxes[b];
     const int nx = B.hi[0] - B.lo[0] + 1, ny = B.hi[1] - B.lo[1] + 1, nz = B.hi[2] - B.lo[2] + 1;
@@ -65,6 +73,12 @@ const WgTab* pa_sweep_wgtab(const pa_level* L, int cls, int tw, int mty, int kse
         int lo[3] = {B.lo[0] + bx * tw, B.lo[1] + by * mty, B.lo[2] + bz * kseg}, hi[3];
         hi[0] = std::min(lo[0] + tw - 1, B.hi[0]); hi[1] = std::min(lo[1] + mty - 1, B.hi[1]); hi[2] = std::min(lo[2] + kseg - 1, B.hi[2]);
         bool early = true;
+        // at a special face (the sweep's own conditions: the first tile on a low side; on a high side the tile that ends at the box's last
+        // cell or one short of it, whose neighbour row / column / plane or the one beyond it is the ghost one): never early
+        for (int d = 0; d < 3 && early; ++d) {
+          if (((sp[(size_t)b] >> (2 * d)) & 1) && lo[d] == B.lo[d]) early = false;
+          if (((sp[(size_t)b] >> (2 * d + 1)) & 1) && hi[d] >= B.hi[d] - 1) early = false;
+        }
         for (int d = 0; d < 3 && early; ++d)
           for (int side = 0; side < 2 && early; ++side) {
             // the slab of the read region beyond face (d, side) of the box (empty when the tile does not come within two cells of it)
@@ -1113,6 +1127,9 @@ int pa_fill_boundary_local_batch_ngs(pa_ctx* ctx, int n, pa_mf* const* Ms, int c
       ms = std::max(ms, max_shell(Ms[i]->lev, ngs[i]));
     }
     if (!Bt.n) continue;
+    // the per-cell form records its launches under tag 3 itself (inside the caller's scope, whose one entry per call is all the region form
+    // leaves): what tells a test that a level without a plan, or PA_FORCE_FALLBACKS, really came this way.  Nothing is recorded unless profiling is on.
+    ProfScope prof(ctx, PA_TAG_FILL);
     hipLaunchKernelGGL(k_fill_boundary, dim3((unsigned)((ms + 255) / 256), (unsigned)Bt.ycum[Bt.n]), dim3(256), 0, ctx->stream, Bt);
   }
   PA_HIP(hipGetLastError());

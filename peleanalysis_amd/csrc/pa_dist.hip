@@ -445,15 +445,19 @@ FbLocal::~FbLocal() {
   if (d_regs) (void)hipFree(d_regs);
   if (d_wgs) (void)hipFree(d_wgs);
 }
+// PA_FORCE_FALLBACKS is looked at on every call, not frozen into the cached plan: under the switch the caller gets a plan that is
+// not ok (it keeps its per-cell kernel), and the level's real plan -- built whatever the switch says -- is there again once it is off
+static FbLocal g_fb_local_off;
+static CpPlan g_cp_off;
 FbLocal* pa_fb_local_plan(pa_ctx* ctx, const pa_level* L, int ng) {
+  if (pa_opt().force_fallbacks) return &g_fb_local_off;
   auto it = L->fb_local.find(ng);
   if (it != L->fb_local.end()) return it->second.get();
   std::unique_ptr<FbLocal> P(new FbLocal());
   FbLocal* raw = P.get();
   L->fb_local[ng] = std::move(P);
   const int n = (int)L->boxes.size();
-  const int on = !pa_opt().force_fallbacks;
-  if (!on || n == 0) return raw;
+  if (n == 0) return raw;
   const auto shifts = domain_shifts(L->domlo, L->domhi, L->is_per);
   std::vector<int> regs, wgs, cand;
   // source boxes that can reach (G - shift): from the level's owner grid (cells of g^3), or all boxes when that grid is
@@ -516,14 +520,14 @@ CpPlan::~CpPlan() {
   if (d_wgs) (void)hipFree(d_wgs);
 }
 CpPlan* pa_cp_plan(pa_ctx* ctx, const pa_level* F, const pa_level* C) {
+  if (pa_opt().force_fallbacks) return &g_cp_off;
   auto it = F->cp_plans.find(C->serial);
   if (it != F->cp_plans.end()) return it->second.get();
   std::unique_ptr<CpPlan> P(new CpPlan());
   CpPlan* raw = P.get();
   F->cp_plans[C->serial] = std::move(P);
-  const int on = !pa_opt().force_fallbacks;
   const int nc = (int)C->boxes.size();
-  if (!on || nc == 0 || F->sfaces.empty()) return raw;
+  if (nc == 0 || F->sfaces.empty()) return raw;
   const auto shifts = domain_shifts(C->domlo, C->domhi, C->is_per);
   const DBox M = {{C->mlo[0], C->mlo[1], C->mlo[2]}, {C->mlo[0] + C->mn[0] * C->g - 1, C->mlo[1] + C->mn[1] * C->g - 1, C->mlo[2] + C->mn[2] * C->g - 1}};
   std::vector<int> regs, wgs, cand;
@@ -962,6 +966,8 @@ int pa_xexchange(pa_ctx* ctx, int njobs, const XJob* jobs) {
       return pa_fail(ctx, "ghost exchange: component range");
     PA_TRY(ensure_buf(ctx, P.sbuf, P.scap, P.send.coff.back() * J.ncomp));
     PA_TRY(ensure_buf(ctx, P.rbuf, P.rcap, P.recv.coff.back() * J.ncomp));
+    // PA_SCRATCH_POISON=1: the receive buffer starts the exchange as NaN (an unpack of cells no peer sent would show)
+    if (pa_opt().scratch_poison && P.rbuf && P.rcap > 0) PA_HIP(hipMemsetAsync(P.rbuf, 0xFF, sizeof(double) * (size_t)P.rcap, ctx->stream));
     // one entry per peer of this plan, peers ascending: both sides walk jobs and peers in the same order
     size_t a = 0, b = 0;
     while (a < P.send.peers.size() || b < P.recv.peers.size()) {

@@ -509,9 +509,31 @@ int pa_level_cg(pa_ctx* ctx, const pa_level* Lc, int nsets) {
   }
   const size_t n = (size_t)std::max<long long>(L->cg_total, 8) * (size_t)nsets;
   PA_HIP(hipMalloc(&L->d_cg, sizeof(double) * n));
-  PA_HIP(hipMemsetAsync(L->d_cg, 0, sizeof(double) * n, ctx->stream));
+  PA_HIP(hipMemsetAsync(L->d_cg, pa_opt().scratch_poison ? 0xFF : 0, sizeof(double) * n, ctx->stream));
   L->cg_sets = nsets;
   L->view.cg = L->d_cg;
+  return 0;
+}
+// PA_SCRATCH_POISON=1: the per-level arrays a pass rewrites before it reads them -- the compact ghost arrays (d_cg) and the compact
+// first-layer arrays the sweep hands to the fix-up (d_ncg) -- start the pass as NaN (all bits set), like the work multifabs of
+// pa_level_scratch.  Queued on the context's stream by the entry of a pass, BEFORE it forks a side stream: a kernel on any stream
+// that reads one of them ahead of the kernel that writes it gets NaN, not what the previous pass left.  d_cp is not touched: its
+// PA_CP_MISSING fill is what the gather's regions rely on.  Nothing is queued with the switch off.
+int pa_poison_level_caches(pa_ctx* ctx, int nlev, pa_mf* const* state) {
+  if (!pa_opt().scratch_poison) return 0;
+  for (int l = 0; l < nlev; ++l) {
+    const pa_level* L = state[l] ? state[l]->lev : nullptr;
+    if (!L) continue;
+    const size_t n1 = (size_t)std::max<long long>(L->cg_total, 8);
+    if (L->d_cg) PA_HIP(hipMemsetAsync(L->d_cg, 0xFF, sizeof(double) * n1 * (size_t)L->cg_sets, ctx->stream));
+    if (L->d_ncg) PA_HIP(hipMemsetAsync(L->d_ncg, 0xFF, sizeof(double) * 6 * n1, ctx->stream));
+  }
+  return 0;
+}
+// ... and a multifab the library keeps between passes (the coarse-source copies of a sharded level)
+int pa_poison_mf(pa_ctx* ctx, pa_mf* m) {
+  if (!pa_opt().scratch_poison || !m || m->total <= 0 || !m->data) return 0;
+  PA_HIP(hipMemsetAsync(m->data, 0xFF, sizeof(double) * (size_t)m->total, ctx->stream));
   return 0;
 }
 // the level's ring items (k_find_ring), built on first use: count, then fill; sorted by (face, position) so that neighbouring threads

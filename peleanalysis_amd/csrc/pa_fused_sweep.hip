@@ -134,7 +134,7 @@ static int level_ncg(pa_ctx* ctx, const pa_level* Lc) {
   if (L->d_ncg) return 0;
   const size_t n = 6 * (size_t)std::max<long long>(L->cg_total, 8);  // three arrays of pairs
   if (hipMalloc(&L->d_ncg, sizeof(double) * n) != hipSuccess) { L->d_ncg = nullptr; return pa_fail(ctx, "compact first-layer arrays: device allocation failed"); }
-  PA_HIP(hipMemsetAsync(L->d_ncg, 0, sizeof(double) * n, ctx->stream));
+  PA_HIP(hipMemsetAsync(L->d_ncg, pa_opt().scratch_poison ? 0xFF : 0, sizeof(double) * n, ctx->stream));
   return 0;
 }
 

@@ -29,7 +29,10 @@ struct pa_options {
   int smooth_march = 1;               // PA_SMOOTH_MARCH=0: the cell-per-thread stencil kernels of the solve
   int smooth_timing = 0;              // PA_SMOOTH_TIMING=1: setup / iteration times of a solve on stderr
   int scratch_poison = 0;             // PA_SCRATCH_POISON=1 (tests): a level's work multifabs (pa_level_scratch: kept between calls, contents undefined) are
-                                      // filled with NaN at every acquisition -- a kernel that reads a cell no step of THIS call wrote shows up in the result
+                                      // filled with NaN at every acquisition -- a kernel that reads a cell no step of THIS call wrote shows up in the result;
+                                      // so are, at allocation and at the start of every fused pass (on the main stream, before a side stream is forked), the
+                                      // per-level arrays a pass rewrites before it reads: the compact ghost arrays (d_cg), the compact first-layer arrays the
+                                      // sweep hands to the fix-up (d_ncg), a sharded level's coarse-source copies and the receive buffer of every exchange
   int force_fallbacks = 0;            // PA_FORCE_FALLBACKS=1 (tests): every path that exists for inputs the tuned one does not take -- FillBoundary /
                                       // patch gather per ghost cell (regions that do not fit a plan), the sweeps group by group (more groups than a
                                       // launch holds), the first form of the marching-cubes cell pass (FABs wider than 819 cells; the switch selects
@@ -346,6 +349,8 @@ int pa_curvopts_level(pa_ctx* ctx, int which, const pa_mf* G, const pa_mf* u, in
 // pa_fused_prep.hip
 int pa_gradcurv_prep_levels(pa_ctx* ctx, int nlev, pa_mf* const* phi, int comp, const pa_mf* const* crse, int ccomp, const int32_t bc[3], double pmin, double pmax, int phase = 3,
                             int nslots = 1, const double* prog = nullptr);
+int pa_poison_level_caches(pa_ctx* ctx, int nlev, pa_mf* const* state);  // PA_SCRATCH_POISON=1: NaN into the levels' d_cg / d_ncg; queues nothing without it
+int pa_poison_mf(pa_ctx* ctx, pa_mf* m);                                 // ... and into a multifab kept between passes (coarse-source copies)
 // pa_fused_sweep.hip
 bool pa_gradcurv_gout_ok(int nlev, pa_mf* const* phi);
 bool pa_gradcurv_parts_ok(int nlev, pa_mf* const* phi);

@@ -266,6 +266,8 @@ static int fused_passes_dist(pa_ctx* ctx, int nlev, pa_mf* const* state, int com
     hipStream_t A = ctx->stream;
     if (!ctx->stream2) PA_HIP(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
     hipStream_t C = ctx->stream2;
+    PA_TRY(pa_poison_level_caches(ctx, nlev, state));  // PA_SCRATCH_POISON=1 only; on A, before C is forked from it
+    for (int l = 1; l < nlev; ++l) { PA_TRY(pa_poison_mf(ctx, csphi[l])); PA_TRY(pa_poison_mf(ctx, csn[l])); }
     while (ctx->sync_evs.size() < 3) {
       hipEvent_t e;
       PA_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -430,6 +432,7 @@ static int exact_passes(pa_ctx* ctx, int nlev, pa_mf* const* state, int comp, co
     // sweeps slowing from 1.94 to 2.15 ms -- they share the memory path -- so everything stays on one stream.)
     std::vector<const pa_mf*> crse(nlev, nullptr), crse_n(nlev, nullptr);
     for (int l = 1; l < nlev; ++l) { crse[l] = state[l - 1]; crse_n[l] = out[l - 1]; }
+    PA_TRY(pa_poison_level_caches(ctx, nlev, state));  // PA_SCRATCH_POISON=1 only; on the main stream, before the side stream is forked from it
     // k_prep_faces (latency bound: dependent lookups, 1.8 TB/s) runs on the side stream NEXT TO FillBoundary (bandwidth
     // bound): it reads valid cells and coarse data and writes the ghost cells of special faces + the compact arrays, FillBoundary
     // writes the ghost cells that are valid cells elsewhere -- disjoint on pure faces, which this pipeline requires.
@@ -708,6 +711,8 @@ extern "C" int pa_gradcurv_run_comps2(pa_ctx* ctx, int nlev, pa_mf* const* state
       if (cs[l]->cs && (!m || !csn[l])) return 1;
       crse[l] = m;
       crse_n[l] = csn[l];
+      PA_TRY(pa_poison_mf(ctx, m));  // PA_SCRATCH_POISON=1 only
+      PA_TRY(pa_poison_mf(ctx, csn[l]));
       jobs.push_back({&cs[l]->x, state[l - 1], comp0, m, 0, ncomps});
     }
     ProfScope prof(ctx, PA_TAG_XCHG);
@@ -730,6 +735,7 @@ extern "C" int pa_gradcurv_run_comps2(pa_ctx* ctx, int nlev, pa_mf* const* state
     }
     // (pageable source: the copy is staged before the call returns, so the host vector may be rewritten for the next batch)
     PA_HIP(hipMemcpyAsync(ctx->d_prog, prog.data(), sizeof(double) * 2 * ns, hipMemcpyHostToDevice, ctx->stream));
+    PA_TRY(pa_poison_level_caches(ctx, nlev, state));  // PA_SCRATCH_POISON=1 only: every batch rewrites what it reads
     PA_TRY(pa_gradcurv_prep_levels(ctx, nlev, state, g0, crse.data(), dist ? g0 - comp0 : g0, bc, pmins[0], pmaxs[0], 3, ns, ctx->d_prog));
     {
       // the sweeps of the batch's components: ONE launch with the slot as a grid dimension

@@ -26,9 +26,14 @@ def _same(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.int64), np.ascontiguousarray(b).view(np.int64))
 
 
+_POISONED = ("nested", "wide", "randu0", "2d")  # these cases' ranks run with PA_SCRATCH_POISON=1: level-owned work arrays start every call as NaN
+
+
 def _worker(rank, world, port, case, transport="gloo"):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    if case in _POISONED:
+        os.environ["PA_SCRATCH_POISON"] = "1"  # before the library reads its switches
     import torch
     import torch.distributed as dist
     torch.cuda.init()  # torch first: one HIP runtime per process
@@ -37,6 +42,7 @@ def _worker(rank, world, port, case, transport="gloo"):
     from peleanalysis_amd import dist as padist
     from peleanalysis_amd.hierarchy import MultiFab, cell_centers, nested_hierarchy
     from test_dist_gloo import scattered_owner
+    from util import SENT_GPU, ref_out, repoison, repoison_comps, sentinel_count, sentinel_note, sentinel_out
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -62,8 +68,8 @@ def _worker(rank, world, port, case, transport="gloo"):
                     s.valid(b)[c] = f(*cell_centers(lv, b, 0), c) + 1e-3 * rng.uniform(-1, 1, size=s.valid(b)[c].shape)
             gst.append(s)
         thr = 0.03 if case == "thr" else None
-        og = [MultiFab(lv, 4, 0) for lv in H.levels]
-        oc = [MultiFab(lv, 17, 0) for lv in H.levels]
+        og = [ref_out(lv, 4) for lv in H.levels]
+        oc = [ref_out(lv, 17) for lv in H.levels]
         O.grad_pipeline(H.levels, [s.copy() for s in gst], 0, bc, og, 0)
         pm = O.curvature_pipeline(H.levels, [s.copy() for s in gst], 0, bc, oc, 0, MultiFab, threshold=thr, do_gauss=True, do_strain=True, strain_tensor=True,
                                   do_velnormal=True, vel_comp=1)
@@ -91,41 +97,51 @@ def _worker(rank, world, port, case, transport="gloo"):
                 got = out[l].download()
                 for i, g in enumerate(dl.gids):
                     for gc, (ref, rc) in pairs.items():
-                        assert _same(got.valid(i)[gc], ref[l].valid(int(g))[rc]), f"rank {rank}/{world} {what}: level {l} box {g} comp {gc} differs from the undistributed oracle"
+                        a, w = got.valid(i)[gc], ref[l].valid(int(g))[rc]
+                        assert _same(a, w), f"rank {rank}/{world} {what}: level {l} box {g} comp {gc} differs from the undistributed oracle{sentinel_note(a, w)}"
 
+        pairs8 = {0: (og, 0), 1: (og, 1), 2: (og, 2), 3: (og, 3), 4: (oc, 2), 5: (oc, 3), 6: (oc, 4), 7: (oc, 1)}
+
+        def early(what):
+            # PA_DIST_EARLY=1 (read per pass): the tiles whose input the local FillBoundary completes are swept on the side stream under
+            # exchange A and the ghost preparation, the others after it -- the same tiles, so the same bits
+            os.environ["PA_DIST_EARLY"] = "1"
+            capi.reload_options()
+            out = [sentinel_out(ctx, dl, 8) for dl in dls]
+            capi.gradcurv_run(ctx, lst, 0, bc, capi.curv_params(threshold=thr, fused=True), work, out, 0)
+            ctx.sync()
+            del os.environ["PA_DIST_EARLY"]
+            capi.reload_options()
+            assert ctx.bc_errors() == 0
+            check(out, pairs8, what)
+
+        # the early-tile pass FIRST, on levels no pass has touched: their compact ghost arrays, rings and plans are cold, so an early tile
+        # that read one of them before the preparation wrote it would not find the right values left there by an earlier pass
+        early("gradcurv fused, early tiles, cold levels")
         # fused and pass-by-pass grad -> curvature; the progress range comes from the min / max reduction over the ranks
         for fused in (True, False):
-            out = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+            out = [sentinel_out(ctx, dl, 8) for dl in dls]
             n0 = comm.nexchange if comm else 0
             capi.gradcurv_run(ctx, lst, 0, bc, capi.curv_params(threshold=thr, fused=fused), work, out, 0)
             ctx.sync()
             assert ctx.bc_errors() == 0
             if comm and fused and not case.startswith("rand"):  # exchange A for every level at once; B (the coarse normals) for every level at once
                 assert comm.nexchange - n0 == 2, "the fused pipeline batches its cross-rank traffic"
-            check(out, {0: (og, 0), 1: (og, 1), 2: (og, 2), 3: (og, 3), 4: (oc, 2), 5: (oc, 3), 6: (oc, 4), 7: (oc, 1)}, f"gradcurv fused={fused}")
-        # PA_DIST_EARLY=1 (read per pass): the tiles whose input the local FillBoundary completes are swept on the side stream under
-        # exchange A and the ghost preparation, the others after it -- the same tiles, so the same bits
-        os.environ["PA_DIST_EARLY"] = "1"
-        capi.reload_options()
-        out = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
-        capi.gradcurv_run(ctx, lst, 0, bc, capi.curv_params(threshold=thr, fused=True), work, out, 0)
-        ctx.sync()
-        del os.environ["PA_DIST_EARLY"]
-        capi.reload_options()
-        assert ctx.bc_errors() == 0
-        check(out, {0: (og, 0), 1: (og, 1), 2: (og, 2), 3: (og, 3), 4: (oc, 2), 5: (oc, 3), 6: (oc, 4), 7: (oc, 1)}, "gradcurv fused, early tiles")
+            check(out, pairs8, f"gradcurv fused={fused}")
+        early("gradcurv fused, early tiles, warm levels")  # and after the non-early passes: the warm case
         # several components at once: exchange A carries all of them, one exchange (B) per component
         if case.startswith("rand"):
             H.levels  # the option / multi-component runs below assume the fixed hierarchies' component layout: skip for random draws
             dist.barrier()
             ctx.close()
             return
-        out = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+        out = [sentinel_out(ctx, dl, 8) for dl in dls]
         seen = {}
 
         def done(c):
             ctx.sync()
             seen[c] = [o.download() for o in out]
+            repoison(out)  # the next component is compared on its own
         n0 = comm.nexchange if comm else 0
         capi.gradcurv_run_comps(ctx, lst, 0, 2, bc, capi.curv_params(prog_min=pm[0], prog_max=pm[1], threshold=thr, fused=True), work, out, 0, done)
         ctx.sync()
@@ -135,15 +151,18 @@ def _worker(rank, world, port, case, transport="gloo"):
         for l, dl in enumerate(dls):
             for i, g in enumerate(dl.gids):
                 v = seen[0][l].valid(i)
+                assert sentinel_count(seen[1][l].valid(i), SENT_GPU) == 0, f"rank {rank}/{world} run_comps: component 1 level {l} box {g}: cells never written by the kernel"
                 assert _same(v[0:4], og[l].valid(int(g))) and _same(v[4:7], oc[l].valid(int(g))[2:5]) and _same(v[7], oc[l].valid(int(g))[1]), \
                     f"rank {rank}/{world} run_comps: level {l} box {g} differs from the undistributed oracle"
         # the same two components as ONE batch (pa_gradcurv_run_comps2): exchange B carries the normals of both slots
-        out2 = [capi.DevMF(ctx, dl, 16, 0) for dl in dls]
+        out2 = [sentinel_out(ctx, dl, 16) for dl in dls]
         seen2 = {}
 
         def done2(c, oc):
             ctx.sync()
             seen2[c] = (oc, [o.download() for o in out2])
+            for o in out2:
+                repoison_comps(o, oc, 8)
         n0 = comm.nexchange if comm else 0
         capi.gradcurv_run_comps2(ctx, lst, 0, 2, bc, capi.curv_params(prog_min=pm[0], prog_max=pm[1], threshold=thr, fused=True), work, out2, 0, 2, done2)
         ctx.sync()
@@ -160,7 +179,7 @@ def _worker(rank, world, port, case, transport="gloo"):
         # (fused=False: pass by pass; fused=True: the sharded exact-normal pipeline's G-output sweeps + one options pass per level where
         # every rank's share takes it -- the ranks agree on the path through one reduction)
         for fused in (False, True):
-            out = [capi.DevMF(ctx, dl, 17, 0) for dl in dls]
+            out = [sentinel_out(ctx, dl, 17) for dl in dls]
             capi.curvature_run(ctx, lst, 0, bc, capi.curv_params(threshold=thr, fused=fused, do_gauss=True, do_strain=True, strain_tensor=True, do_velnormal=True,
                                                                 vel_comp=1), out, 0)
             ctx.sync()
@@ -171,7 +190,7 @@ def _worker(rank, world, port, case, transport="gloo"):
             if fused and case in ("wide", "thr", "sym", "sfc", "scatter"):  # nested hierarchies: every rank's share takes the all-levels sweeps
                 assert path == 1, f"rank {rank}/{world} case {case}: the sharded options pass fell back to the pass-by-pass kernels"
         # the gradient tool's pipeline
-        out = [capi.DevMF(ctx, dl, 4, 0) for dl in dls]
+        out = [sentinel_out(ctx, dl, 4) for dl in dls]
         capi.grad_run(ctx, lst, 0, bc, out, 0)
         ctx.sync()
         check(out, {c: (og, c) for c in range(4)}, "grad_run")
@@ -198,6 +217,8 @@ def _smooth_worker(rank, world, port, case, transport="gloo"):
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     replicated = case.endswith("+rep")
     case = case.replace("+rep", "")
+    if case in _POISONED:
+        os.environ["PA_SCRATCH_POISON"] = "1"  # before the library reads its switches
     if replicated:
         os.environ["PA_SMOOTH_REPLICATED"] = "1"  # read once, when the library first solves
     import torch
@@ -208,6 +229,7 @@ def _smooth_worker(rank, world, port, case, transport="gloo"):
     from peleanalysis_amd import dist as padist
     from peleanalysis_amd.hierarchy import MultiFab, cell_centers, nested_hierarchy
     from test_dist_gloo import scattered_owner
+    from util import sentinel_out
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -268,7 +290,7 @@ def _smooth_worker(rank, world, port, case, transport="gloo"):
             for i, g in enumerate(dl.gids):
                 s.valid(i)[...] = rhs[l].valid(int(g))
             drhs.append(capi.DevMF.from_host(ctx, dl, s))
-            dsol.append(capi.DevMF(ctx, dl, 1, 0))
+            dsol.append(sentinel_out(ctx, dl, 1))
         n0 = comm.nexchange if comm else 0
         it, res = capi.smooth_solve(ctx, drhs, 0, dsol, 0, dt, bc, tol=1e-13 if stiff else 1e-14, maxiter=200)
         if stiff:
@@ -293,7 +315,7 @@ def _smooth_worker(rank, world, port, case, transport="gloo"):
         if replicated:  # same input, same kernels, fixed summation order (the reflux of a concave corner included): the ONE-RANK solve's bits
             ols = [capi.DevLevel(ctx, lv) for lv in H.levels]
             orhs = [capi.DevMF.from_host(ctx, dl, r) for dl, r in zip(ols, rhs)]
-            osol = [capi.DevMF(ctx, dl, 1, 0) for dl in ols]
+            osol = [sentinel_out(ctx, dl, 1) for dl in ols]
             it1, res1 = capi.smooth_solve(ctx, orhs, 0, osol, 0, dt, bc, tol=1e-13 if stiff else 1e-14, maxiter=200)
             assert (it1, res1) == (it, res), ((it1, res1), (it, res))
             one = [m.download() for m in osol]

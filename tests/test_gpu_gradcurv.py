@@ -8,7 +8,8 @@ import pytest
 
 from peleanalysis_amd import capi
 from peleanalysis_amd.hierarchy import MultiFab
-from util import CONFIGS, assert_valid_bits_equal, build_config, make_states, rel_err
+from util import (CONFIGS, assert_no_sentinel, assert_untouched, assert_valid_bits_equal, build_config, make_states, ref_out, rel_err, repoison,
+                  repoison_comps, sentinel_out)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,11 +29,11 @@ def test_grad_run_matches_oracle(ctx, oracle, name):
     bc = capi.bc_from_flags(per, sym)
     # oracle (reference-shaped multipass)
     ost = [s.copy() for s in states]
-    oout = [MultiFab(lv, 4, 0) for lv in H.levels]
+    oout = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, ost, 0, bc, oout, 0, multipass=True)
     # HIP
     dls, dst = _dev(ctx, H, states)
-    dout = [capi.DevMF(ctx, dl, 4, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 4) for dl in dls]
     capi.grad_run(ctx, dst, 0, bc, dout, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0
@@ -49,10 +50,10 @@ def test_curvature_run_pass_by_pass_matches_oracle(ctx, oracle, name, threshold)
     H, per, sym, fn = build_config(name)
     states = make_states(H, 1, 2, fn, seed=5)
     bc = capi.bc_from_flags(per, sym)
-    oout = [MultiFab(lv, 5, 0) for lv in H.levels]
+    oout = [ref_out(lv, 5) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oout, 0, MultiFab, threshold=threshold)
     dls, dst = _dev(ctx, H, states)
-    dout = [capi.DevMF(ctx, dl, 5, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 5) for dl in dls]
     capi.curvature_run(ctx, dst, 0, bc, capi.curv_params(threshold=threshold, fused=False), dout, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0
@@ -67,13 +68,13 @@ def test_gradcurv_fused_matches_oracle(ctx, oracle, name, threshold):
     H, per, sym, fn = build_config(name)
     states = make_states(H, 1, 2, fn, seed=7)
     bc = capi.bc_from_flags(per, sym)
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=True)
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, threshold=threshold)
     dls, dst = _dev(ctx, H, states)
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 8) for dl in dls]
     capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(threshold=threshold, fused=True), work, dout, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0
@@ -98,13 +99,13 @@ def test_gradcurv_fused_wide_boxes(ctx, oracle, threshold, pipeline, options):
     assert all(lv.boxes[:, 3].max() - lv.boxes[:, 0].min() + 1 == 128 and ((lv.boxes[:, 3] - lv.boxes[:, 0] + 1) == 64).all() for lv in H.levels)
     states = make_states(H, 1, 2, field_flame, seed=23)
     bc = capi.bc_from_flags((1, 1, 0), (0, 0, 0))
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=True)
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, threshold=threshold)
     dls, dst = _dev(ctx, H, states)
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 8) for dl in dls]
     capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(threshold=threshold, fused=True), work, dout, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0
@@ -125,15 +126,16 @@ def test_gradcurv_exact_normal_pipeline(ctx, oracle, per, sym, threshold):
     H = nested_hierarchy(96, 3, 48, is_per=per)
     states = make_states(H, 1, 2, field_flame, seed=29)
     bc = capi.bc_from_flags(per, sym)
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=False)
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, threshold=threshold)
     dls, dst = _dev(ctx, H, states)
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 8) for dl in dls]
     slow_seen = []
-    for rep in range(2):  # the second pass reuses the level's compact arrays
+    for rep in range(2):  # the second pass reuses the level's compact arrays; it is compared on its own, not with what the first left
+        repoison(dout)
         # with a threshold the sweep clips N and K itself and the one-layer fix-up recomputes the clipped normals it needs
         # (curvature.cpp:549-570; the coarse normals under coarse-fine faces stay clipped: quirk Q2)
         capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(threshold=threshold, fused=True), work, dout, 0)
@@ -164,11 +166,12 @@ def test_clip_fixup_general_path_is_exercised(ctx, oracle):
     bc = capi.bc_from_flags((1, 1, 0), (0, 0, 0))
     dls, dst = _dev(ctx, H, states)
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 8) for dl in dls]
     total = 0
     for thr in (0.02, 0.1, 0.25, 0.4):
-        oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+        oc = [ref_out(lv, 5) for lv in H.levels]
         oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, threshold=thr)
+        repoison(dout)
         capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(threshold=thr, fused=True), work, dout, 0)
         ctx.sync()
         n = ctx.lib.pa_last_slow_cells(ctx.h)
@@ -191,13 +194,13 @@ def test_gradcurv_exact_normal_pipeline_one_short_tiles(ctx, oracle, per):
     H = Hierarchy([l0, l1], 2)
     states = make_states(H, 1, 2, field_flame, seed=37)
     bc = capi.bc_from_flags(per, (0, 0, 0))
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=False)
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab)
     dls, dst = _dev(ctx, H, states)
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 8) for dl in dls]
     capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(fused=True), work, dout, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0
@@ -220,12 +223,13 @@ def test_gradcurv_four_levels_many_components(ctx, oracle):
     bc = capi.bc_from_flags((1, 1, 0), (0, 0, 0))
     dls, dst = _dev(ctx, H, states)
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 8) for dl in dls]
     for c in range(ncomp):
-        og = [MultiFab(lv, 4, 0) for lv in H.levels]
+        og = [ref_out(lv, 4) for lv in H.levels]
         oracle.grad_pipeline(H.levels, [s.copy() for s in states], c, bc, og, 0, multipass=True)
-        oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+        oc = [ref_out(lv, 5) for lv in H.levels]
         oracle.curvature_pipeline(H.levels, [s.copy() for s in states], c, bc, oc, 0, MultiFab)
+        repoison(dout)
         capi.gradcurv_run(ctx, dst, c, bc, capi.curv_params(fused=True), work, dout, 0)
         ctx.sync()
         assert ctx.bc_errors() == 0
@@ -254,13 +258,13 @@ def test_gradcurv_fused_ragged_shapes(ctx, oracle, dom, maxbox, per, monkeypatch
     H = Hierarchy([Level(np.array(boxes, dtype=np.int32), lo, hi, per, (0, 0, 0), (1, 1, 1))], 2)
     states = make_states(H, 1, 2, field_trig, seed=5)
     bc = capi.bc_from_flags(per, (0, 0, 0))
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=True)
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, threshold=0.02)
     dls, dst = _dev(ctx, H, states)
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 8) for dl in dls]
     capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(threshold=0.02, fused=True), work, dout, 0)
     ctx.sync()
     got = dout[0].download()
@@ -268,7 +272,7 @@ def test_gradcurv_fused_ragged_shapes(ctx, oracle, dom, maxbox, per, monkeypatch
     assert_valid_bits_equal(got, oc[0], [(4, 2), (5, 3), (6, 4), (7, 1)], f"ragged {dom} curv")
     # the gradient tool's own kernels (k_grad_march above 32 columns, k_grad_marchn below)
     dls2, dst2 = _dev(ctx, H, states)
-    dgr = [capi.DevMF(ctx, dl, 4, 0) for dl in dls2]
+    dgr = [sentinel_out(ctx, dl, 4) for dl in dls2]
     capi.grad_run(ctx, dst2, 0, bc, dgr, 0)
     ctx.sync()
     assert_valid_bits_equal(dgr[0].download(), og[0], [(c, c) for c in range(4)], f"ragged {dom} grad_run")
@@ -301,11 +305,11 @@ def test_per_fab_entry_points(ctx, oracle):
     states = make_states(H, 1, 2, fn, seed=13)
     bc = capi.bc_from_flags(per, sym)
     oracle.fill_boundary(states[0], 0, 1, 2)
-    og = MultiFab(lv, 4, 0)
+    og = ref_out(lv, 4)
     oracle.grad_fused(states[0], 0, og, 0, True)
     dl = capi.DevLevel(ctx, lv)
     dphi = capi.DevMF.from_host(ctx, dl, states[0])
-    dout = capi.DevMF(ctx, dl, 4, 0)
+    dout = sentinel_out(ctx, dl, 4)
     dxinv = capi._d3(1.0 / lv.dx)
     for b in range(lv.nboxes):
         fp, fo = dphi.fab(b), dout.fab(b)
@@ -336,13 +340,13 @@ def test_concave_coarse_fine_corner_falls_back_to_passes(ctx, oracle):
     per, sym = (1, 0, 1), (0, 1, 0)
     states = make_states(H, 1, 2, field_flame, seed=17)
     bc = capi.bc_from_flags(per, sym)
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0)
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, threshold=0.03)
     dls, dst = _dev(ctx, H, states)
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 8) for dl in dls]
     capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(threshold=0.03, fused=True), work, dout, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0
@@ -358,11 +362,11 @@ def test_curvature_options_match_oracle(ctx, oracle, name):
     H, per, sym, fn = build_config(name)
     states = make_states(H, 4, 2, fn, seed=23)  # comp 0 = progress source, 1..3 = velocity
     bc = capi.bc_from_flags(per, sym)
-    oout = [MultiFab(lv, 17, 0) for lv in H.levels]
+    oout = [ref_out(lv, 17) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oout, 0, MultiFab, threshold=0.05, do_gauss=True, vel_comp=1,
                               do_strain=True, do_velnormal=True, strain_tensor=True)
     dls, dst = _dev(ctx, H, states)
-    dout = [capi.DevMF(ctx, dl, 17, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 17) for dl in dls]
     # the work multifabs of both paths live as long as the level does: a first call on OTHER data leaves them full of stale values
     other = make_states(H, 4, 2, fn, seed=77)
     for m in other:
@@ -373,8 +377,7 @@ def test_curvature_options_match_oracle(ctx, oracle, name):
     ctx.sync()
     # fused=False: pass by pass; fused=True: Progress / K / N from the exact-normal pipeline's G-output sweeps + one options pass per level
     for fused in (False, True, False):
-        for m in dout:
-            m.setval(-7.0)
+        repoison(dout)
         P = capi.curv_params(threshold=0.05, fused=fused, do_gauss=True, do_strain=True, strain_tensor=True, do_velnormal=True, vel_comp=1)
         capi.curvature_run(ctx, dst, 0, bc, P, dout, 0)
         ctx.sync()
@@ -384,14 +387,13 @@ def test_curvature_options_match_oracle(ctx, oracle, name):
     # the work multifabs kept with the levels can be released (and come back on the next call)
     freed = sum(int(ctx.lib.pa_level_free_scratch(dl.h)) for dl in dls)
     assert freed > 0 and sum(int(ctx.lib.pa_level_free_scratch(dl.h)) for dl in dls) == 0
-    for m in dout:
-        m.setval(-7.0)
+    repoison(dout)
     capi.curvature_run(ctx, dst, 0, bc, capi.curv_params(threshold=0.05, fused=True, do_gauss=True, do_strain=True, strain_tensor=True, do_velnormal=True, vel_comp=1), dout, 0)
     ctx.sync()
     for l in range(H.nlev):
         assert_valid_bits_equal(dout[l].download(), oout[l], [(c, c) for c in range(17)], f"{name} options after pa_level_free_scratch, level {l}")
     # too few output components are rejected before any launch
-    small = [capi.DevMF(ctx, dl, 6, 0) for dl in dls]
+    small = [sentinel_out(ctx, dl, 6) for dl in dls]
     with pytest.raises(capi.PaError):
         capi.curvature_run(ctx, dst, 0, bc, P, small, 0)
 
@@ -407,16 +409,16 @@ def test_deep_hierarchies_take_the_fused_pipelines(ctx, oracle, nlev, base, box)
     assert H.nlev == nlev
     states = make_states(H, 4, 2, field_flame, seed=3)
     bc = capi.bc_from_flags(per)
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=False)
-    oo = [MultiFab(lv, 17, 0) for lv in H.levels]
+    oo = [ref_out(lv, 17) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oo, 0, MultiFab, threshold=0.03, do_gauss=True, vel_comp=1, do_strain=True,
                               do_velnormal=True, strain_tensor=True)
-    ou = [MultiFab(lv, 5, 0) for lv in H.levels]
+    ou = [ref_out(lv, 5) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, ou, 0, MultiFab)
     dls, dst = _dev(ctx, H, states)
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    d8 = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    d8 = [sentinel_out(ctx, dl, 8) for dl in dls]
     capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(fused=True), work, d8, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0
@@ -426,12 +428,12 @@ def test_deep_hierarchies_take_the_fused_pipelines(ctx, oracle, nlev, base, box)
         got = d8[l].download()
         assert_valid_bits_equal(got, og[l], [(c, c) for c in range(4)], f"{nlev} levels: grad level {l}")
         assert_valid_bits_equal(got, ou[l], [(4, 2), (5, 3), (6, 4), (7, 1)], f"{nlev} levels: curvature level {l}")
-    d4 = [capi.DevMF(ctx, dl, 4, 0) for dl in dls]  # the gradient tool's pass (64-row boxes: the all-levels gradient launch, in chunks too)
+    d4 = [sentinel_out(ctx, dl, 4) for dl in dls]  # the gradient tool's pass (64-row boxes: the all-levels gradient launch, in chunks too)
     capi.grad_run(ctx, dst, 0, bc, d4, 0)
     ctx.sync()
     for l in range(nlev):
         assert_valid_bits_equal(d4[l].download(), og[l], [(c, c) for c in range(4)], f"{nlev} levels: grad_run level {l}")
-    d17 = [capi.DevMF(ctx, dl, 17, 0) for dl in dls]
+    d17 = [sentinel_out(ctx, dl, 17) for dl in dls]
     capi.curvature_run(ctx, dst, 0, bc, capi.curv_params(threshold=0.03, fused=True, do_gauss=True, do_strain=True, strain_tensor=True, do_velnormal=True, vel_comp=1), d17, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0 and ctx.lib.pa_curvature_last_path(ctx.h) in (1, 2)
@@ -450,24 +452,28 @@ def test_gradcurv_run_comps_equals_component_by_component(ctx, oracle):
         bc = capi.bc_from_flags((1, 1, 0))
         dls, dst = _dev(ctx, H, states)
         work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-        dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+        dout = [sentinel_out(ctx, dl, 8) for dl in dls]
         want = {}
         for c in (1, 2, 3):
+            repoison(dout)
             capi.gradcurv_run(ctx, dst, c, bc, capi.curv_params(fused=True), work, dout, 0)
             ctx.sync()
-            want[c] = [d.download().data.copy() for d in dout]
+            want[c] = [d.download() for d in dout]
         dst2 = [capi.DevMF.from_host(ctx, dl, st) for dl, st in zip(dls, states)]  # fresh ghost cells, same levels
         got = {}
 
         def done(c):
             ctx.sync()
-            got[c] = [d.download().data.copy() for d in dout]
+            got[c] = [d.download() for d in dout]
+            repoison(dout)  # the next component starts from an output no earlier one wrote
+        repoison(dout)
         capi.gradcurv_run_comps(ctx, dst2, 1, 3, bc, capi.curv_params(fused=True), work, dout, 0, done)
         ctx.sync()
         assert ctx.bc_errors() == 0 and sorted(got) == [1, 2, 3]
         for c in (1, 2, 3):
             for l in range(H.nlev):
-                assert np.array_equal(got[c][l].view(np.int64), want[c][l].view(np.int64)), (base, c, l)
+                assert_no_sentinel(want[c][l], range(8), f"pa_gradcurv_run, boxes of {box}, comp {c} level {l}")
+                assert_valid_bits_equal(got[c][l], want[c][l], [(k, k) for k in range(8)], f"pa_gradcurv_run_comps, boxes of {box}, comp {c} level {l}")
 
 
 @pytest.mark.parametrize("threshold", [None, 0.1])
@@ -489,21 +495,24 @@ def test_gradcurv_run_comps_batched_equals_component_by_component(ctx, oracle, n
     bc = capi.bc_from_flags((1, 1, 0))
     dls, dst = _dev(ctx, H, states)
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 8) for dl in dls]
     params = capi.curv_params(threshold=threshold, fused=True)
     want = {}
     for c in range(ncomp):
+        repoison(dout)
         capi.gradcurv_run(ctx, dst, c, bc, params, work, dout, 0)
         ctx.sync()
         want[c] = [d.download() for d in dout]
     dst2 = [capi.DevMF.from_host(ctx, dl, st) for dl, st in zip(dls, states)]  # fresh ghost cells, same levels
     nslot = min(nbatch, ncomp)
-    dout2 = [capi.DevMF(ctx, dl, 3 + 8 * nslot, 0) for dl in dls]
+    dout2 = [sentinel_out(ctx, dl, 3 + 8 * nslot) for dl in dls]
     got = {}
 
     def done(c, oc):
         ctx.sync()
         got[c] = (oc, [d.download() for d in dout2])
+        for d in dout2:  # the slot goes to a component of the next batch: that one starts from SENT_GPU as well
+            repoison_comps(d, oc, 8)
     capi.gradcurv_run_comps2(ctx, dst2, 0, ncomp, bc, params, work, dout2, 3, nbatch, done)
     ctx.sync()
     assert ctx.bc_errors() == 0 and sorted(got) == list(range(ncomp))
@@ -515,6 +524,9 @@ def test_gradcurv_run_comps_batched_equals_component_by_component(ctx, oracle, n
         for l in range(H.nlev):
             for b in range(H.levels[l].nboxes):
                 assert np.array_equal(mfs[l].fab(b)[oc:oc + 8].view(np.int64), want[c][l].fab(b)[0:8].view(np.int64)), (nbatch, c, l, b)
+            assert_no_sentinel(want[c][l], range(8), f"pa_gradcurv_run comp {c} level {l}")
+            assert_no_sentinel(mfs[l], range(oc, oc + 8), f"pa_gradcurv_run_comps2 comp {c} level {l}")
+            assert_untouched(mfs[l], range(3), f"components below ocomp are not pa_gradcurv_run_comps2's, level {l}")
 
 
 def test_gradcurv_run_comps2_arguments(ctx):
@@ -527,7 +539,7 @@ def test_gradcurv_run_comps2_arguments(ctx):
     dls, dst = _dev(ctx, H, states)
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
     params = capi.curv_params(fused=True)
-    out16 = [capi.DevMF(ctx, dl, 16, 0) for dl in dls]
+    out16 = [sentinel_out(ctx, dl, 16) for dl in dls]
     seen = []
     capi.gradcurv_run_comps2(ctx, dst, 0, 2, bc, params, work, out16, 0, 99, lambda c, oc: seen.append((c, oc)))  # 99 -> 2 slots
     capi.gradcurv_run_comps2(ctx, dst, 2, 1, bc, params, work, out16, 8, 0, lambda c, oc: seen.append((c, oc)))   # 0 -> 1 slot, at ocomp 8
@@ -555,6 +567,54 @@ def test_switched_off_paths_still_match(ctx):
     assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
 
+def test_force_fallbacks_is_read_at_every_call_not_when_a_level_first_makes_its_plans(ctx, oracle, options):
+    """PA_FORCE_FALLBACKS flipped through the `options` fixture on levels that already hold their FillBoundary and coarse-patch plans
+    (pa_fb_local_plan / pa_cp_plan keep the plan and decide per call): off, on, off on ONE set of levels and one state, each pass into a
+    re-poisoned output and bit-equal to the oracle.  That the "on" pass really took the fallbacks is read off the launch counts of the
+    sweep (tag 1: group by group under the switch -- five levels, more than one launch holds) and of FillBoundary (tag 3: the per-cell
+    kernel records its own launches inside the pass's one entry): they differ from the "off" pass and equal those of levels CREATED under the switch."""
+    H, per, sym, fn = build_config("amr5_wall_z")
+    states = make_states(H, 1, 2, fn, seed=7)
+    bc = capi.bc_from_flags(per, sym)
+    og = [ref_out(lv, 4) for lv in H.levels]
+    oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=True)
+    oc = [ref_out(lv, 5) for lv in H.levels]
+    oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, threshold=0.05)
+
+    def run(what, dls, dst, work, dout):
+        repoison(dout)
+        ctx.sync()
+        ctx.profile_read(1, reset=True)  # (a reset drops the records of every tag)
+        capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(threshold=0.05, fused=True), work, dout, 0)
+        ctx.sync()
+        assert ctx.bc_errors() == 0
+        counts = {1: ctx.profile_read(1)[0], 3: ctx.profile_read(3, reset=True)[0]}
+        print(f"{what}: launches by tag {counts}")
+        for l in range(H.nlev):
+            got = dout[l].download()
+            assert_valid_bits_equal(got, og[l], [(c, c) for c in range(4)], f"{what}: grad level {l}")
+            assert_valid_bits_equal(got, oc[l], [(4, 2), (5, 3), (6, 4), (7, 1)], f"{what}: curv level {l}")
+        return counts
+
+    def fresh():
+        dls, dst = _dev(ctx, H, states)
+        return dls, dst, [capi.DevMF(ctx, dl, 1, 2) for dl in dls], [sentinel_out(ctx, dl, 8) for dl in dls]
+    ctx.profile_enable(True)
+    try:
+        kept = fresh()
+        off1 = run("switch off, new levels", *kept)
+        options(PA_FORCE_FALLBACKS=1)
+        on = run("switch on, the same levels", *kept)
+        made_on = run("switch on, levels created under it", *fresh())
+        options(PA_FORCE_FALLBACKS=None)
+        off2 = run("switch off again, the same levels", *kept)
+    finally:
+        ctx.profile_enable(False)
+    assert on == made_on, (on, made_on)
+    assert on[1] != off1[1] and on[3] != off1[3], (on, off1)
+    assert off2 == off1, (off2, off1)
+
+
 def test_not_properly_nested_fine_level_is_counted_on_every_path(ctx):
     """a level-2 region that touches the edge of level 1 (no buffer cells): its ghost cells beyond that edge have no coarse
     parent.  The library never aborts -- it counts those ghost cells (pa_bc_errors; the tools turn a non-zero count into the
@@ -576,11 +636,14 @@ def test_not_properly_nested_fine_level_is_counted_on_every_path(ctx):
     bc = capi.bc_from_flags((0, 0, 0))
     dls, dst = _dev(ctx, H, states)
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 8) for dl in dls]
     counts = {}
+    outs = {}
     for sw in ("1", "2"):
+        repoison(dout)
         capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(prog_min=200.0, prog_max=2100.0, fused=True), work, dout, 0)
         ctx.sync()
+        outs[sw] = [d.download() for d in dout]
         kn = ctx.lib.pa_sweep_kernel_name(ctx.h).decode()
         assert kn.endswith("CG=1>") or "_levels<" in kn, kn
         counts[sw] = ctx.bc_errors()
@@ -589,6 +652,10 @@ def test_not_properly_nested_fine_level_is_counted_on_every_path(ctx):
     assert ctx.bc_errors() > 0  # pass by pass: counted as well (its own number of passes over those cells)
     # three faces of 64 x 64 ghost cells sit beyond level 1, counted once by the prep and once by the fix-up of phi's and n's ghosts
     assert counts["1"] == counts["2"] == 26088, counts
+    # there is no oracle for an input the reference aborts on; but the second (warm) pass stores what the first stored, into every cell
+    for l in range(H.nlev):
+        assert_no_sentinel(outs["1"][l], range(8), f"first pass, level {l}")
+        assert_valid_bits_equal(outs["2"][l], outs["1"][l], [(c, c) for c in range(8)], f"second pass against the first, level {l}")
 
 
 def test_work_multifabs_are_never_read_before_they_are_written():
@@ -603,6 +670,15 @@ def test_work_multifabs_are_never_read_before_they_are_written():
     env = dict(os.environ, PA_SCRATCH_POISON="1")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_gpu_gradcurv.py"), os.path.join(here, "test_gpu_smooth.py"), os.path.join(here, "test_gpu_random.py"),
                         "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider", "-k", "curvature_run or options or curvature_options or smoothing or gauss or strain"],
+                       env=env, capture_output=True, text=True, cwd=os.path.dirname(here))
+    assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    # the same switch covers the per-level arrays of the fused passes that "every pass rewrites before it reads": the compact ghost
+    # arrays, the compact first-layer arrays the sweep hands to the fix-up (NaN when they are allocated and at the start of every pass,
+    # on the main stream before a side stream is forked) -- a second child over the fused paths, against the oracle bit for bit
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_gpu_gradcurv.py"), os.path.join(here, "test_gpu_production_geometry.py"),
+                        "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider", "-k",
+                        "fused_matches_oracle or exact_normal_pipeline or wide_boxes or chunked_face_kernels or ragged_shapes or deep_hierarchies or run_comps "
+                        "or test_gpu_production_geometry"],
                        env=env, capture_output=True, text=True, cwd=os.path.dirname(here))
     assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
@@ -638,12 +714,12 @@ def test_chunked_face_kernels_odd_origins_small_faces_and_slots(ctx, oracle, per
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
     want = {}
     for c in range(ncomp):
-        og = [MultiFab(lv, 4, 0) for lv in H.levels]
-        oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+        og = [ref_out(lv, 4) for lv in H.levels]
+        oc = [ref_out(lv, 5) for lv in H.levels]
         oracle.grad_pipeline(H.levels, [s.copy() for s in states], c, bc, og, 0, multipass=True)
         oracle.curvature_pipeline(H.levels, [s.copy() for s in states], c, bc, oc, 0, MultiFab)
         want[c] = (og, oc)
-        dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+        dout = [sentinel_out(ctx, dl, 8) for dl in dls]
         capi.gradcurv_run(ctx, dst, c, bc, capi.curv_params(fused=True), work, dout, 0)
         ctx.sync()
         assert ctx.bc_errors() == 0
@@ -654,7 +730,7 @@ def test_chunked_face_kernels_odd_origins_small_faces_and_slots(ctx, oracle, per
             assert_valid_bits_equal(got, oc[l], [(4, 2), (5, 3), (6, 4), (7, 1)], f"comp {c} curv level {l}")
     # the same three components as one batch
     dst2 = [capi.DevMF.from_host(ctx, dl, st) for dl, st in zip(dls, states)]
-    dout2 = [capi.DevMF(ctx, dl, 8 * ncomp, 0) for dl in dls]
+    dout2 = [sentinel_out(ctx, dl, 8 * ncomp) for dl in dls]
     capi.gradcurv_run_comps2(ctx, dst2, 0, ncomp, bc, capi.curv_params(fused=True), work, dout2, 0, ncomp, None)
     ctx.sync()
     assert ctx.bc_errors() == 0
@@ -667,9 +743,9 @@ def test_chunked_face_kernels_odd_origins_small_faces_and_slots(ctx, oracle, per
     # the gradient tool's applyBC goes through the same kernel (PHIONLY) on a state with ONE ghost layer
     st1 = make_states(H, 1, 1, field_flame, seed=91)
     dst1 = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, st1)]
-    og1 = [MultiFab(lv, 4, 0) for lv in H.levels]
+    og1 = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in st1], 0, bc, og1, 0, multipass=True)
-    dgr = [capi.DevMF(ctx, dl, 4, 0) for dl in dls]
+    dgr = [sentinel_out(ctx, dl, 4) for dl in dls]
     capi.grad_run(ctx, dst1, 0, bc, dgr, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0
@@ -689,28 +765,28 @@ def test_gaussian_curvature_inside_the_sweep(ctx, oracle, per, sym, base, box, t
     H = nested_hierarchy(base, 3, box, is_per=per)
     states = make_states(H, 4, 2, field_flame, seed=29)
     bc = capi.bc_from_flags(per, sym)
-    oo = [MultiFab(lv, 17, 0) for lv in H.levels]
+    oo = [ref_out(lv, 17) for lv in H.levels]
     opts = dict(do_gauss=True, do_strain=True, strain_tensor=True, do_velnormal=True)
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oo, 0, MultiFab, threshold=threshold, vel_comp=1, **opts)
     dls, dst = _dev(ctx, H, states)
     for fused, want_path in ((True, 2), (False, 0)):
-        d17 = [capi.DevMF(ctx, dl, 17, 0) for dl in dls]
-        for m in d17:
-            m.setval(-5.0)
+        d17 = [sentinel_out(ctx, dl, 17) for dl in dls]
         capi.curvature_run(ctx, dst, 0, bc, capi.curv_params(threshold=threshold, fused=fused, vel_comp=1, **opts), d17, 0)
         ctx.sync()
         assert ctx.bc_errors() == 0 and ctx.lib.pa_curvature_last_path(ctx.h) == want_path
         for l in range(H.nlev):
             assert_valid_bits_equal(d17[l].download(), oo[l], [(c, c) for c in range(17)], f"fused={fused} level {l}")
     # the Gaussian curvature alone (no strain / velocity pass at all)
-    og = [MultiFab(lv, 17, 0) for lv in H.levels]
+    og = [ref_out(lv, 17) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, MultiFab, threshold=threshold, vel_comp=1, do_gauss=True)
-    d17 = [capi.DevMF(ctx, dl, 17, 0) for dl in dls]
+    d17 = [sentinel_out(ctx, dl, 17) for dl in dls]
     capi.curvature_run(ctx, dst, 0, bc, capi.curv_params(threshold=threshold, fused=True, vel_comp=1, do_gauss=True), d17, 0)
     ctx.sync()
     assert ctx.lib.pa_curvature_last_path(ctx.h) == 2
     for l in range(H.nlev):
-        assert_valid_bits_equal(d17[l].download(), og[l], [(c, c) for c in range(6)], f"gauss only, level {l}")
+        got = d17[l].download()
+        assert_valid_bits_equal(got, og[l], [(c, c) for c in range(6)], f"gauss only, level {l}")
+        assert_untouched(got, range(6, 17), f"gauss only: the components of the options that are off, level {l}")
 
 
 @pytest.mark.parametrize("per,layout", [((0, 0, 0), 0), ((1, 0, 0), 0), ((0, 0, 0), 1)])
@@ -738,10 +814,10 @@ def test_gaussian_curvature_inside_the_sweep_staggered_boxes(ctx, oracle, per, l
     bc = capi.bc_from_flags(per, (0, 0, 0))
     opts = dict(do_gauss=True, do_strain=True, strain_tensor=True, do_velnormal=True)
     for threshold in (None, 0.05):
-        oo = [MultiFab(lv, 17, 0) for lv in H.levels]
+        oo = [ref_out(lv, 17) for lv in H.levels]
         oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oo, 0, MultiFab, threshold=threshold, vel_comp=1, **opts)
         dls, dst = _dev(ctx, H, states)
-        d17 = [capi.DevMF(ctx, dl, 17, 0) for dl in dls]
+        d17 = [sentinel_out(ctx, dl, 17) for dl in dls]
         capi.curvature_run(ctx, dst, 0, bc, capi.curv_params(threshold=threshold, fused=True, vel_comp=1, **opts), d17, 0)
         ctx.sync()
         assert ctx.bc_errors() == 0 and ctx.lib.pa_curvature_last_path(ctx.h) == 2
@@ -760,10 +836,10 @@ def test_gaussian_curvature_inside_the_sweep_single_level(ctx, oracle, per, sym)
     states = make_states(H, 4, 2, field_flame, seed=3)
     bc = capi.bc_from_flags(per, sym)
     opts = dict(do_gauss=True, do_strain=True, strain_tensor=True, do_velnormal=True)
-    oo = [MultiFab(lv, 17, 0) for lv in H.levels]
+    oo = [ref_out(lv, 17) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oo, 0, MultiFab, threshold=0.03, vel_comp=1, **opts)
     dls, dst = _dev(ctx, H, states)
-    d17 = [capi.DevMF(ctx, dl, 17, 0) for dl in dls]
+    d17 = [sentinel_out(ctx, dl, 17) for dl in dls]
     capi.curvature_run(ctx, dst, 0, bc, capi.curv_params(threshold=0.03, fused=True, vel_comp=1, **opts), d17, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0 and ctx.lib.pa_curvature_last_path(ctx.h) == 2
@@ -779,12 +855,14 @@ def test_gaussian_curvature_inside_the_sweep_five_levels(ctx, oracle):
     states = make_states(H, 4, 2, field_flame, seed=77)
     bc = capi.bc_from_flags((0, 1, 0), (1, 0, 0))
     opts = dict(do_gauss=True, do_strain=True, do_velnormal=True)
-    oo = [MultiFab(lv, 17, 0) for lv in H.levels]
+    oo = [ref_out(lv, 17) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oo, 0, MultiFab, threshold=None, vel_comp=1, **opts)
     dls, dst = _dev(ctx, H, states)
-    d17 = [capi.DevMF(ctx, dl, 17, 0) for dl in dls]
+    d17 = [sentinel_out(ctx, dl, 17) for dl in dls]
     capi.curvature_run(ctx, dst, 0, bc, capi.curv_params(threshold=None, fused=True, vel_comp=1, **opts), d17, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0 and ctx.lib.pa_curvature_last_path(ctx.h) == 2
     for l in range(H.nlev):
-        assert_valid_bits_equal(d17[l].download(), oo[l], [(c, c) for c in range(8)], f"level {l}")
+        got = d17[l].download()
+        assert_valid_bits_equal(got, oo[l], [(c, c) for c in range(8)], f"level {l}")
+        assert_untouched(got, range(8, 17), f"the strain tensor is off: its components, level {l}")

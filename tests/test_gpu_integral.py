@@ -298,7 +298,7 @@ def test_error_paths(ctx):
         with pytest.raises(capi.PaError, match="weight must be positive"):
             acc.add_level(mf1, None, 1, 1, 2.0 * w[0])
         with pytest.raises(capi.PaError, match="must hold 3 components"):
-            with capi.DevMF(ctx, dl1, 2, 0) as small:
+            with capi.DevMF(ctx, dl1, 2, 0) as small:  # an input, refused for its component count before anything reads it
                 acc.add_level(small, None, 1, 1, w[1])
         # a scale taken from a magnitude the data exceed: the read fails instead of returning a wrapped sum
         acc.begin(w[0], [1.0] * 3)

@@ -151,8 +151,8 @@ def _sharded_worker(rank, world, port):
                 lst.append(cp.DevMF.from_host(ctx, dl, s))
             own += lst
             work = [cp.DevMF(ctx, dl, 1, 2) for dl in dls]
-            out8 = [cp.DevMF(ctx, dl, 8, 0) for dl in dls]
-            out18 = [cp.DevMF(ctx, dl, 18, 0) for dl in dls]
+            out8 = [cp.DevMF(ctx, dl, 8, 0) for dl in dls]  # written, never compared: this test counts device memory, not values
+            out18 = [cp.DevMF(ctx, dl, 18, 0) for dl in dls]  # likewise
             own += work + out8 + out18
             cp.gradcurv_run(ctx, lst, 0, bc, cp.curv_params(fused=True), work, out8, 0)
             cp.gradcurv_run(ctx, lst, 0, bc, cp.curv_params(fused=False), work, out8, 0)

@@ -11,7 +11,7 @@ import pytest
 
 from peleanalysis_amd import capi
 from peleanalysis_amd.hierarchy import MultiFab, chop_box, field_flame, fill_analytic, nested_hierarchy, Hierarchy, Level
-from util import assert_filter_parity, assert_valid_bits_equal
+from util import assert_filter_parity, assert_valid_bits_equal, ref_out, sentinel_out
 
 pytestmark = pytest.mark.gpu
 
@@ -36,14 +36,14 @@ def test_gradcurv_128_boxes_three_levels_matches_oracle(ctx, oracle, thr):
             v = s.valid(b)
             v += 1e-3 * rng.uniform(-1, 1, size=v.shape)
         states.append(s)
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=False, omp=True)
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, prog_min=300.0, prog_max=2000.0, threshold=thr, omp=True)
     dls = [capi.DevLevel(ctx, lv) for lv in H.levels]
     dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, states)]
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 8) for dl in dls]
     capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(prog_min=300.0, prog_max=2000.0, threshold=thr, fused=True), work, dout, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0
@@ -54,7 +54,7 @@ def test_gradcurv_128_boxes_three_levels_matches_oracle(ctx, oracle, thr):
         assert_valid_bits_equal(got, og[l], [(c, c) for c in range(4)], f"128^3 boxes thr {thr} grad level {l}")
         assert_valid_bits_equal(got, oc[l], [(4, 2), (5, 3), (6, 4), (7, 1)], f"128^3 boxes thr {thr} curv level {l}")
     # the gradient tool's sweep (k_grad_march<13>) on the same boxes
-    dgr = [capi.DevMF(ctx, dl, 4, 0) for dl in dls]
+    dgr = [sentinel_out(ctx, dl, 4) for dl in dls]
     capi.grad_run(ctx, dst, 0, bc, dgr, 0)
     ctx.sync()
     for l in range(H.nlev):
@@ -118,14 +118,14 @@ def test_box_filter_128_boxes_matches_oracle(ctx, oracle, filter_mode, fgr):
     for b in range(lv.nboxes):
         v = ins.valid(b)
         v += 1e-3 * rng.uniform(-1, 1, size=v.shape)
-    oin, oout = ins.copy(), MultiFab(lv, 1, 0)
+    oin, oout = ins.copy(), ref_out(lv, 1)
     info = oracle.filter_pipeline(H.levels, [oin], [oout], 1, base_fgr=fgr, same_fgr_all_levels=True, omp=True)
     assert info[0] == (fgr, ngf)
     dl = capi.DevLevel(ctx, lv)
     din = capi.DevMF.from_host(ctx, dl, ins)
     ctx.check(ctx.lib.pa_fill_boundary(ctx.h, din.h, 0, 1, ngf))
     ctx.check(ctx.lib.pa_foextrap(ctx.h, din.h, 0, 1, ngf))
-    dout = capi.DevMF(ctx, dl, 1, 0)
+    dout = sentinel_out(ctx, dl, 1)
     w = (C.c_double * (2 * ngf + 1))()
     assert ctx.lib.pa_box_filter_weights(fgr, w) == ngf
     ctx.check(ctx.lib.pa_boxfilter_level(ctx.h, din.h, dout.h, 0, 1, ngf, w))
@@ -155,8 +155,8 @@ def test_gradcurv_tagged_irregular_hierarchy_matches_oracle(ctx, oracle):
             v += 1e-3 * rng.uniform(-1, 1, size=v.shape)
         states.append(s)
     thr = 0.04
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=False, omp=True)
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, prog_min=300.0, prog_max=2000.0, threshold=thr, omp=True)
     dls = [capi.DevLevel(ctx, lv) for lv in H.levels]
@@ -165,7 +165,7 @@ def test_gradcurv_tagged_irregular_hierarchy_matches_oracle(ctx, oracle):
     dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, states)]
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
     for fused in (True, False):
-        dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+        dout = [sentinel_out(ctx, dl, 8) for dl in dls]
         capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(prog_min=300.0, prog_max=2000.0, threshold=thr, fused=fused), work, dout, 0)
         ctx.sync()
         assert ctx.bc_errors() == 0
@@ -216,9 +216,7 @@ def test_x_face_mirror_of_the_sweep_gives_the_same_bits(ctx, oracle, shape, monk
     for v in ("0", "1"):
         monkeypatch.setenv("PA_NCG", v)
         capi.reload_options()
-        dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
-        for m in dout:
-            m.setval(-3.0)
+        dout = [sentinel_out(ctx, dl, 8) for dl in dls]
         capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(prog_min=300.0, prog_max=2000.0, fused=True), work, dout, 0)
         ctx.sync()
         assert ctx.bc_errors() == 0
@@ -231,8 +229,8 @@ def test_x_face_mirror_of_the_sweep_gives_the_same_bits(ctx, oracle, shape, monk
         for b in range(lv.nboxes):
             assert np.array_equal(outs["0"][l].valid(b).view(np.int64), outs["1"][l].valid(b).view(np.int64)), (shape, l, b)
     _omp()
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=False, omp=True)
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, prog_min=300.0, prog_max=2000.0, omp=True)
     for l in range(H.nlev):

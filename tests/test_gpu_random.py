@@ -7,7 +7,7 @@ import pytest
 
 from peleanalysis_amd import capi
 from peleanalysis_amd.hierarchy import Hierarchy, Level, MultiFab, chop_box, field_flame, field_trig
-from util import assert_filter_parity, assert_valid_bits_equal, make_states
+from util import assert_filter_parity, assert_untouched, assert_valid_bits_equal, make_states, ref_out, repoison, sentinel_out
 
 pytestmark = pytest.mark.gpu
 
@@ -77,16 +77,16 @@ def test_random_hierarchy_matches_oracle(ctx, oracle, seed):
     thr = None if seed % 3 else 0.03
     states = make_states(H, 1, 2, fn, seed=seed)
     bc = capi.bc_from_flags(per, sym)
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=True)
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, threshold=thr)
     tag = f"seed {seed}: {[tuple(lv.domhi + 1) for lv in H.levels]} per {per} sym {sym} boxes {[lv.nboxes for lv in H.levels]}"
     for fused in (True, False):
         dls = [capi.DevLevel(ctx, lv) for lv in H.levels]
         dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, states)]
         work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-        dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+        dout = [sentinel_out(ctx, dl, 8) for dl in dls]
         capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(threshold=thr, fused=fused), work, dout, 0)
         ctx.sync()
         assert ctx.bc_errors() == 0, tag
@@ -97,7 +97,7 @@ def test_random_hierarchy_matches_oracle(ctx, oracle, seed):
     # the gradient tool's own pipeline (1 ghost layer is enough for it)
     dls = [capi.DevLevel(ctx, lv) for lv in H.levels]
     dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, states)]
-    dgr = [capi.DevMF(ctx, dl, 4, 0) for dl in dls]
+    dgr = [sentinel_out(ctx, dl, 4) for dl in dls]
     capi.grad_run(ctx, dst, 0, bc, dgr, 0)
     ctx.sync()
     for l in range(H.nlev):
@@ -184,7 +184,7 @@ def test_random_hierarchy_isosurface_and_filter(ctx, oracle, filter_mode, seed):
         for b in range(lv.nboxes):
             ins[l].valid(b)[:] = fields[l].valid(b)
     oin = [m.copy() for m in ins]
-    oouts = [MultiFab(lv, 2, 0) for lv in H.levels]
+    oouts = [ref_out(lv, 2) for lv in H.levels]
     info = oracle.filter_pipeline(H.levels, oin, oouts, 2, base_fgr=base_fgr, same_fgr_all_levels=True, interp_type=interp)
     for l, lv in enumerate(H.levels):
         din = capi.DevMF.from_host(ctx, dls[l], ins[l])
@@ -194,7 +194,7 @@ def test_random_hierarchy_isosurface_and_filter(ctx, oracle, filter_mode, seed):
         if l > 0:
             ctx.check(ctx.lib.pa_fillpatch_two_levels(ctx.h, din.h, dprev.h, 0, 2, ngl[l], 2, interp))
         ctx.check(ctx.lib.pa_foextrap(ctx.h, din.h, 0, 2, ngl[l]))
-        dout = capi.DevMF(ctx, dls[l], 2, 0)
+        dout = sentinel_out(ctx, dls[l], 2)
         fgr, ngf = info[l]
         w = (C.c_double * (2 * ngf + 1))()
         assert ctx.lib.pa_box_filter_weights(fgr, w) == ngf == ngl[l]
@@ -213,15 +213,14 @@ def test_random_hierarchy_curvature_options(ctx, oracle, seed):
     thr = None if seed % 2 else 0.04
     states = make_states(H, 4, 2, fn, seed=seed + 5)  # comp 0 = progress source, 1..3 = velocity
     bc = capi.bc_from_flags(per, sym)
-    oout = [MultiFab(lv, 17, 0) for lv in H.levels]
+    oout = [ref_out(lv, 17) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oout, 0, MultiFab, threshold=thr, do_gauss=True, vel_comp=1, do_strain=True,
                               do_velnormal=True, strain_tensor=True)
     dls = [capi.DevLevel(ctx, lv) for lv in H.levels]
     dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, states)]
-    dout = [capi.DevMF(ctx, dl, 17, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 17) for dl in dls]
     for fused in (False, True):  # pass by pass / the exact-normal pipeline's G-output sweeps + one options pass per level
-        for m in dout:
-            m.setval(-7.0)
+        repoison(dout)
         P = capi.curv_params(threshold=thr, fused=fused, do_gauss=True, do_strain=True, strain_tensor=True, do_velnormal=True, vel_comp=1)
         capi.curvature_run(ctx, dst, 0, bc, P, dout, 0)
         ctx.sync()
@@ -244,13 +243,11 @@ def test_random_wide_box_curvature_options_fast_path(ctx, oracle, seed, which):
     comps = dict(all=list(range(17)), gauss=[0, 1, 2, 3, 4, 5], strain_veln=[0, 1, 2, 3, 4, 6, 7], veln=[0, 1, 2, 3, 4, 7])[which]
     states = make_states(H, 4, 2, fn, seed=seed + 5)
     bc = capi.bc_from_flags(per, sym)
-    oout = [MultiFab(lv, 17, 0) for lv in H.levels]
+    oout = [ref_out(lv, 17) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oout, 0, MultiFab, threshold=thr, vel_comp=1, **opts)
     dls = [capi.DevLevel(ctx, lv) for lv in H.levels]
     dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, states)]
-    dout = [capi.DevMF(ctx, dl, 17, 0) for dl in dls]
-    for m in dout:
-        m.setval(-7.0)
+    dout = [sentinel_out(ctx, dl, 17) for dl in dls]
     capi.curvature_run(ctx, dst, 0, bc, capi.curv_params(threshold=thr, fused=True, vel_comp=1, **opts), dout, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0
@@ -259,9 +256,7 @@ def test_random_wide_box_curvature_options_fast_path(ctx, oracle, seed, which):
     for l in range(H.nlev):
         got = dout[l].download()
         assert_valid_bits_equal(got, oout[l], [(c, c) for c in comps], f"wide seed {seed} options {which} level {l}")
-        for c in set(range(17)) - set(comps):
-            for b in range(H.levels[l].nboxes):
-                assert np.all(got.valid(b)[c] == -7.0), f"wide seed {seed} options {which}: component {c} was written"
+        assert_untouched(got, sorted(set(range(17)) - set(comps)), f"wide seed {seed} options {which}: the components of the options that are off")
 
 
 def _draw_wide(seed):
@@ -296,15 +291,15 @@ def test_random_wide_box_hierarchy_matches_oracle(ctx, oracle, seed):
     assert H.nlev >= 2 and min(int((lv.boxes[:, 3] - lv.boxes[:, 0]).min()) + 1 for lv in H.levels) > 16
     states = make_states(H, 1, 2, fn, seed=seed)
     bc = capi.bc_from_flags(per, sym)
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=False)
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab)
     tag = f"wide seed {seed}: {[tuple(lv.domhi + 1) for lv in H.levels]} per {per} sym {sym} boxes {[(lv.nboxes, int((lv.boxes[:, 3] - lv.boxes[:, 0]).max()) + 1) for lv in H.levels]}"
     dls = [capi.DevLevel(ctx, lv) for lv in H.levels]
     dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, states)]
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 8) for dl in dls]
     capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(fused=True), work, dout, 0)
     ctx.sync()
     assert ctx.bc_errors() == 0, tag
@@ -337,16 +332,16 @@ def test_random_union_hierarchy_matches_oracle(ctx, oracle, seed):
     thr = None if seed % 3 else 0.03
     states = make_states(H, 1, 2, fn, seed=seed)
     bc = capi.bc_from_flags(per, sym)
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=True)
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, threshold=thr)
     tag = f"union seed {seed}: {[tuple(lv.domhi + 1) for lv in H.levels]} per {per} sym {sym} boxes {[lv.nboxes for lv in H.levels]}"
     for fused in (True, False):
         dls = [capi.DevLevel(ctx, lv) for lv in H.levels]
         dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, states)]
         work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-        dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+        dout = [sentinel_out(ctx, dl, 8) for dl in dls]
         capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(threshold=thr, fused=fused), work, dout, 0)
         ctx.sync()
         assert ctx.bc_errors() == 0, tag
@@ -357,7 +352,7 @@ def test_random_union_hierarchy_matches_oracle(ctx, oracle, seed):
             got = dout[l].download()
             assert_valid_bits_equal(got, og[l], [(c, c) for c in range(4)], f"{tag} fused {fused} grad level {l}")
             assert_valid_bits_equal(got, oc[l], [(4, 2), (5, 3), (6, 4), (7, 1)], f"{tag} fused {fused} curv level {l}")
-    dgr = [capi.DevMF(ctx, dl, 4, 0) for dl in dls]
+    dgr = [sentinel_out(ctx, dl, 4) for dl in dls]
     capi.grad_run(ctx, dst, 0, bc, dgr, 0)
     ctx.sync()
     for l in range(H.nlev):
@@ -410,14 +405,14 @@ def test_random_union_wide_box_hierarchy_matches_oracle(ctx, oracle, seed):
     tag = f"union-wide seed {seed}: {[tuple(lv.domhi + 1) for lv in H.levels]} per {per} sym {sym} boxes {[(lv.nboxes, int((lv.boxes[:, 3] - lv.boxes[:, 0]).max()) + 1) for lv in H.levels]}"
     og, oc = [], []
     for c in range(2):
-        og.append([MultiFab(lv, 4, 0) for lv in H.levels])
-        oc.append([MultiFab(lv, 5, 0) for lv in H.levels])
+        og.append([ref_out(lv, 4) for lv in H.levels])
+        oc.append([ref_out(lv, 5) for lv in H.levels])
         oracle.grad_pipeline(H.levels, [s.copy() for s in states], c, bc, og[c], 0, multipass=False)
         oracle.curvature_pipeline(H.levels, [s.copy() for s in states], c, bc, oc[c], 0, MultiFab, threshold=thr)
     dls = [capi.DevLevel(ctx, lv) for lv in H.levels]
     dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, states)]
     work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-    dout = [capi.DevMF(ctx, dl, 16, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 16) for dl in dls]
     nirr = sum(ctx.lib.pa_level_irregular_cells(ctx.h, dl.h) for dl in dls)
     capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(threshold=thr, fused=True), work, dout, 0)
     ctx.sync()
@@ -428,6 +423,8 @@ def test_random_union_wide_box_hierarchy_matches_oracle(ctx, oracle, seed):
         got = dout[l].download()
         assert_valid_bits_equal(got, og[0][l], [(c, c) for c in range(4)], f"{tag} ({nirr} irregular cells) grad level {l}")
         assert_valid_bits_equal(got, oc[0][l], [(4, 2), (5, 3), (6, 4), (7, 1)], f"{tag} ({nirr} irregular cells) curv level {l}")
+        assert_untouched(got, range(8, 16), f"{tag}: the second slot is not pa_gradcurv_run's, level {l}")
+    repoison(dout)
     capi.gradcurv_run_comps2(ctx, dst, 0, 2, bc, capi.curv_params(threshold=thr, fused=True), work, dout, 0, 2)
     ctx.sync()
     assert ctx.bc_errors() == 0, tag

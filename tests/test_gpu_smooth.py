@@ -9,6 +9,7 @@ import pytest
 
 from peleanalysis_amd import capi
 from peleanalysis_amd.hierarchy import MultiFab, Level, chop_box, nested_hierarchy, fill_analytic, field_flame
+from util import assert_no_sentinel, assert_untouched, ref_out, sentinel_out
 
 pytestmark = pytest.mark.gpu
 
@@ -16,9 +17,18 @@ pytestmark = pytest.mark.gpu
 def _solve_gpu(ctx, levels, rhs, dt, bc, tol):
     dls = [capi.DevLevel(ctx, lv) for lv in levels]
     drhs = [capi.DevMF.from_host(ctx, dl, r) for dl, r in zip(dls, rhs)]
-    dsol = [capi.DevMF(ctx, dl, 1, 0) for dl in dls]
+    dsol = [sentinel_out(ctx, dl, 1) for dl in dls]
     it, res = capi.smooth_solve(ctx, drhs, 0, dsol, 0, dt, bc, tol=tol, maxiter=200)
-    return [d.download() for d in dsol], it, res
+    return _written([d.download() for d in dsol]), it, res
+
+
+def _written(sol):
+    """the solution multifabs started as SENT_GPU: every valid cell was stored, with a finite value (the comparisons that follow are to a
+    tolerance, which a NaN would fail only by the accident of `<=`)"""
+    for l, m in enumerate(sol):
+        assert_no_sentinel(m, [0], f"pa_smooth_solve, level {l}")
+        assert np.isfinite(m.valid_concat(0)).all(), f"pa_smooth_solve, level {l}: non-finite values"
+    return sol
 
 
 def test_smooth_single_level_eigenmode(ctx):
@@ -70,11 +80,11 @@ def test_curvature_run_with_smoothing(ctx, oracle, per, sym):
     states = make_states(H, 1, 2, field_flame, seed=41)
     bc = capi.bc_from_flags(per, sym)
     dt = 1e-3
-    oout = [MultiFab(lv, 18, 0) for lv in H.levels]
+    oout = [ref_out(lv, 18) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oout, 0, MultiFab, do_smooth=True, smoothing_time=dt, smooth_tol=1e-14)
     dls = [capi.DevLevel(ctx, lv) for lv in H.levels]
     dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, states)]
-    dout = [capi.DevMF(ctx, dl, 18, 0) for dl in dls]
+    dout = [sentinel_out(ctx, dl, 18) for dl in dls]
     capi.curvature_run(ctx, dst, 0, bc, capi.curv_params(fused=False, do_smooth=True, smoothing_time=dt), dout, 0)
     ctx.sync()
     assert ctx.lib.pa_curvature_last_path(ctx.h) == 0
@@ -84,9 +94,7 @@ def test_curvature_run_with_smoothing(ctx, oracle, per, sym):
     dst4 = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, st4)]
     both = []
     for fused in (False, True):
-        o = [capi.DevMF(ctx, dl, 18, 0) for dl in dls]
-        for m in o:
-            m.setval(-7.0)
+        o = [sentinel_out(ctx, dl, 18) for dl in dls]
         capi.curvature_run(ctx, dst4, 0, bc, capi.curv_params(threshold=0.04, fused=fused, do_smooth=True, smoothing_time=dt, do_gauss=True, do_strain=True,
                                                              strain_tensor=True, do_velnormal=True, vel_comp=1), o, 0)
         ctx.sync()
@@ -95,8 +103,13 @@ def test_curvature_run_with_smoothing(ctx, oracle, per, sym):
     for l, lv in enumerate(H.levels):
         for b in range(lv.nboxes):
             assert np.array_equal(both[0][l].valid(b).view(np.int64), both[1][l].valid(b).view(np.int64)), f"do_smooth + options: fast path != pass by pass, level {l} box {b}"
+        for m in (both[0][l], both[1][l]):  # equal bits are no proof that either path stored them
+            assert_no_sentinel(m, range(18), f"do_smooth + options, level {l}")
     for l, lv in enumerate(H.levels):
         g = dout[l].download()
+        assert_no_sentinel(g, [0, 1, 2, 3, 4, 17], f"do_smooth, level {l} (kernel output)")
+        assert_no_sentinel(oout[l], [0, 1, 2, 3, 4, 17], f"do_smooth, level {l} (oracle output)")
+        assert_untouched(g, range(6, 17), f"do_smooth without options: their components, level {l}")
         for b in range(lv.nboxes):
             gv, wv = g.valid(b), oout[l].valid(b)
             assert np.array_equal(gv[0].view(np.int64), wv[0].view(np.int64)), "Progress (unsmoothed) must stay bit-identical"
@@ -143,7 +156,7 @@ def test_curvature_run_with_smoothing(ctx, oracle, per, sym):
         sm.append(m)
     dsm = [capi.DevMF.from_host(ctx, dl, m) for dl, m in zip(dls, sm)]
     for fused in (False, True):
-        o = [capi.DevMF(ctx, dl, 18, 0) for dl in dls]
+        o = [sentinel_out(ctx, dl, 18) for dl in dls]
         capi.curvature_run(ctx, dsm, 0, bc, capi.curv_params(prog_min=0.0, prog_max=1.0, fused=fused), o, 0)
         ctx.sync()
         for l, lv in enumerate(H.levels):
@@ -211,13 +224,13 @@ def test_smooth_and_stream_reject_bad_input(ctx):
     l0 = Level(chop_box((0, 0, 0), (15, 15, 15), 8), (0, 0, 0), (15, 15, 15), (1, 1, 1), (0, 0, 0), (1, 1, 1))
     l1 = Level(np.array([[9, 8, 8, 18, 23, 23]], dtype=np.int32), (0, 0, 0), (31, 31, 31), (1, 1, 1), (0, 0, 0), (1, 1, 1))  # odd lo: not ratio-aligned
     dls = [capi.DevLevel(ctx, l0), capi.DevLevel(ctx, l1)]
-    rhs = [capi.DevMF(ctx, dl, 1, 0) for dl in dls]
-    sol = [capi.DevMF(ctx, dl, 1, 0) for dl in dls]
+    rhs = [capi.DevMF(ctx, dl, 1, 0) for dl in dls]  # inputs of calls that are refused before any launch: never read
+    sol = [capi.DevMF(ctx, dl, 1, 0) for dl in dls]  # never written
     with pytest.raises(capi.PaError, match="aligned"):
         capi.smooth_solve(ctx, rhs, 0, sol, 0, 1e-3, (0, 0, 0))
     with pytest.raises(capi.PaError, match="component"):
         capi.smooth_solve(ctx, rhs[:1], 3, sol[:1], 0, 1e-3, (0, 0, 0))
-    v = [capi.DevMF(ctx, dls[0], 3, 0)]  # no ghost layers
+    v = [capi.DevMF(ctx, dls[0], 3, 0)]  # input (refused): no ghost layers
     with pytest.raises(capi.PaError, match="nGrow"):
         capi.stream_trace(ctx, v, 0, np.array([[0.5, 0.5, 0.5]]), 5, 0.01)
     v = [capi.DevMF(ctx, dls[0], 2, 2)]  # too few components
@@ -251,13 +264,13 @@ def test_smooth_multigrid_preconditioner(ctx, oracle, per, base, box, monkeypatc
         else:
             monkeypatch.delenv("PA_SMOOTH_MG")
         capi.reload_options()
-        dsol = [capi.DevMF(ctx, dl, 1, 0) for dl in dls]
+        dsol = [sentinel_out(ctx, dl, 1) for dl in dls]
         it, res = capi.smooth_solve(ctx, drhs, 0, dsol, 0, dt, bc, tol=1e-13, maxiter=2000)
         assert res <= 1e-13
-        out[mg] = ([d.download() for d in dsol], it)
+        out[mg] = (_written([d.download() for d in dsol]), it)
     assert out["1"][1] == out[""][1], "dt / dx^2 = 100: the preconditioner is the default"
     # pa_curvature_run iterates to 1e-14 (and accepts 1e-12): the preconditioned recurrence gets there too, in a handful of iterations
-    dsol = [capi.DevMF(ctx, dl, 1, 0) for dl in dls]
+    dsol = [sentinel_out(ctx, dl, 1) for dl in dls]
     it14, res14 = capi.smooth_solve(ctx, drhs, 0, dsol, 0, dt, bc, tol=1e-14, maxiter=100)
     assert res14 <= 1e-14 and it14 <= out["1"][1] + 6, (it14, res14)
     assert out["1"][1] * 3 <= out["0"][1], f"iterations: preconditioned {out['1'][1]}, plain {out['0'][1]}"
@@ -299,10 +312,10 @@ def test_smooth_wide_boxes_marching_kernels(ctx, oracle, dtq, base, monkeypatch)
     for march, kz in variants:
         monkeypatch.setenv("PA_SMOOTH_MARCH", march)
         capi.reload_options()
-        dsol = [capi.DevMF(ctx, dl, 1, 0) for dl in dls]
+        dsol = [sentinel_out(ctx, dl, 1) for dl in dls]
         it, res = capi.smooth_solve(ctx, drhs, 0, dsol, 0, dt, bc, tol=1e-13, maxiter=500)
         assert res <= 1e-13
-        out[(march, kz)] = ([d.download() for d in dsol], it, res)
+        out[(march, kz)] = (_written([d.download() for d in dsol]), it, res)
     monkeypatch.delenv("PA_SMOOTH_MARCH")
     capi.reload_options()
     ref = out[variants[0]]
@@ -357,9 +370,9 @@ def _solve(ctx, H, rhs, dt, bc, tol, maxiter=2000):
     """every call builds its own DevLevels and DevMFs"""
     dls = [capi.DevLevel(ctx, lv) for lv in H.levels]
     drhs = [capi.DevMF.from_host(ctx, dl, r) for dl, r in zip(dls, rhs)]
-    dsol = [capi.DevMF(ctx, dl, 1, 0) for dl in dls]
+    dsol = [sentinel_out(ctx, dl, 1) for dl in dls]
     it, res = capi.smooth_solve(ctx, drhs, 0, dsol, 0, dt, bc, tol=tol, maxiter=maxiter)
-    return [d.download() for d in dsol], it, res
+    return _written([d.download() for d in dsol]), it, res
 
 
 @pytest.mark.parametrize("q", [2.0, 100.0])  # the plain iteration / the V-cycle-preconditioned one (the default above q = 8)

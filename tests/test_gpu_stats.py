@@ -358,7 +358,7 @@ def test_error_paths(ctx):
         with pytest.raises(capi.PaError, match="binMax must be greater than binMin"):
             acc.add_level(mf, None, 1, (0, 0, 0, 15, 15, 15), 1, 5.0, 5.0)
         with pytest.raises(capi.PaError, match="the bin component and 2 averaged ones"):
-            with capi.DevMF(ctx, dl, 2, 0) as small:
+            with capi.DevMF(ctx, dl, 2, 0) as small:  # an input, refused for its component count before anything reads it
                 acc.add_level(small, None, 1, (0, 0, 0, 15, 15, 15), 1, 0.0, 1.0)
         bad = st[0].copy()
         bad.valid(3)[1, 2, 2, 2] = np.inf

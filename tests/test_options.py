@@ -26,7 +26,7 @@ FLIPPED_BY = {
     "PA_SMOOTH_MARCH": "tests/test_gpu_smooth.py::test_smooth_wide_boxes_marching_kernels",
     "PA_SMOOTH_TIMING": "tests/test_options.py::test_smooth_timing_and_tool_exit",
     "PA_SCRATCH_POISON": "tests/test_gpu_gradcurv.py::test_work_multifabs_are_never_read_before_they_are_written",
-    "PA_FORCE_FALLBACKS": "tests/test_gpu_gradcurv.py::test_switched_off_paths_still_match, test_gpu_filter_mc.py (tiles: the first form of the marching-cubes cell pass, per level and inside pa_mc_hierarchy_fine; fillpatch)",
+    "PA_FORCE_FALLBACKS": "tests/test_gpu_gradcurv.py::test_switched_off_paths_still_match, ::test_force_fallbacks_is_read_at_every_call... (flipped on existing levels), test_gpu_filter_mc.py (tiles: the first form of the marching-cubes cell pass, per level and inside pa_mc_hierarchy_fine; fillpatch)",
     # the tools' own (tools/common, tools/src)
     "PA_HOST_THP": "tests/test_plotfile_tools.py::test_cpp_template_tool_large_level_with_and_without_huge_pages",
     "PA_IO_THREADS": "tests/test_sanitizers.py",

@@ -13,7 +13,7 @@ import pytest
 
 from peleanalysis_amd.hierarchy import Hierarchy, Level, MultiFab, regrid_copy, retile_level, union_hierarchy, _occupancy
 from test_gpu_random import _draw
-from util import bits_equal, make_states
+from util import bits_equal, make_states, ref_out, sentinel_out
 from peleanalysis_amd.hierarchy import field_flame, field_trig
 
 
@@ -129,9 +129,9 @@ def _on_tiling(states, T, ng):
 
 def _oracle_all(oracle, H, states, per, sym, thr):
     bc = oracle.bc_from_flags(per, sym)
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=True)
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, threshold=thr)
     return _dense(og, [0, 1, 2, 3]), _dense(oc, [0, 1, 2, 3, 4])
 
@@ -163,7 +163,7 @@ def test_oracle_filter_is_invariant_under_retiling(oracle, seed, interp):
             m = MultiFab(tv, 2, ngs[l], fill=np.nan)
             regrid_copy(f, m)
             ins.append(m)
-        outs = [MultiFab(tv, 2, 0) for tv in T.levels]
+        outs = [ref_out(tv, 2) for tv in T.levels]
         oracle.filter_pipeline(T.levels, ins, outs, 2, base_fgr=2, interp_type=interp)
         return _dense(outs, [0, 1])
 
@@ -187,9 +187,9 @@ def test_retiled_device_path_matches_oracle_on_the_file_boxes(ctx, oracle, seed)
     thr = None if seed % 3 else 0.04
     states = make_states(H, 1, 2, fn, seed=seed)
     bc = capi.bc_from_flags(per, sym)
-    og = [MultiFab(lv, 4, 0) for lv in H.levels]
+    og = [ref_out(lv, 4) for lv in H.levels]
     oracle.grad_pipeline(H.levels, [s.copy() for s in states], 0, bc, og, 0, multipass=True)
-    oc = [MultiFab(lv, 5, 0) for lv in H.levels]
+    oc = [ref_out(lv, 5) for lv in H.levels]
     oracle.curvature_pipeline(H.levels, [s.copy() for s in states], 0, bc, oc, 0, MultiFab, threshold=thr)
     rng = np.random.default_rng(seed)
     mx = tuple(int(v) for v in rng.choice([12, 16, 24, 1000], size=3))
@@ -199,7 +199,7 @@ def test_retiled_device_path_matches_oracle_on_the_file_boxes(ctx, oracle, seed)
         dls = [capi.DevLevel(ctx, lv) for lv in T.levels]
         dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, tst)]
         work = [capi.DevMF(ctx, dl, 1, 2) for dl in dls]
-        dout = [capi.DevMF(ctx, dl, 8, 0) for dl in dls]
+        dout = [sentinel_out(ctx, dl, 8) for dl in dls]
         capi.gradcurv_run(ctx, dst, 0, bc, capi.curv_params(threshold=thr, fused=fused), work, dout, 0)
         ctx.sync()
         assert ctx.bc_errors() == 0
