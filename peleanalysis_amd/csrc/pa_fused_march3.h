@@ -10,12 +10,20 @@
 //     previous plane go out in ONE burst at the top of the step, and every role issues its request for the
 //     plane three steps ahead right AFTER the plane's barrier -- loads and stores never sit next to each other
 //     in a wave's instruction stream.  With the requests at the top of the step, directly in front of the
-//     stores (the first v3 schedule, kept as DBG 256 for A/B), the same kernel takes 2.27 ms; moving only the
-//     output rows' request behind the barrier gives 2.02-2.10, all roles 1.97, plus the burst 1.92.
+//     stores (the first v3 schedule; its diagnostic build went in round 11), the same kernel takes 2.27 ms; moving
+//     only the output rows' request behind the barrier gives 2.02-2.10, all roles 1.97, plus the burst 1.92.
 //   * every role keeps THREE planes in flight (f0,f1,f2): the plane consumed in a step was
-//     requested three steps earlier, so a step waits only for stores that are >= 4 planes old
-//     (`vmcnt(26)`); the loop is unrolled by 3 = the LDS ring period, which also makes every ring
-//     slot a compile-time LDS offset and keeps the in-flight registers free of moves;
+//     requested three steps earlier, so an output row's step waits with the 2 requests and 16 stores of
+//     the two steps before it still in flight (`s_waitcnt vmcnt(18)` in each of the loop's three steps:
+//     tests/test_sweep_isa.py holds the compiler to it); the loop is unrolled by 3 = the LDS ring
+//     period, which also makes every ring slot a compile-time LDS offset and keeps the in-flight
+//     registers free of moves;
+//   * PROLOGUE OF AN OUTPUT ROW (round 11): the first three steps of a segment (planes k0-1, k0, k0+1) have no
+//     result to store and are compiled without the burst; then one group of three storing steps is peeled in
+//     front of the loop.  Before, those steps stored junk to plane k0 (3 x 8 stores per row and segment that the
+//     same thread overwrote later), and because one wait count must hold on every edge into the loop the
+//     prologue's requests were drained first (one exposed round trip per segment) -- which the exact-normal
+//     variants' z-face loads, issued after the drain, defeated: their loops waited 18, 9, none.
 //   * global addresses are a wave-uniform base (SGPR pair, advanced with scalar adds) plus one
 //     loop-invariant 32-bit lane offset: no per-store 64-bit vector address arithmetic;
 //   * the z-direction face fluxes of c, phi and n_z are carried from plane to plane (the high face
@@ -78,37 +86,8 @@ __device__ __forceinline__ double favg(double fl, double fh) { return -(0.5 * (f
 #define PA_OPAQUE(x) asm volatile("" : "+v"(x))
 #define PA_LDG(base, off) (*(const double*)((const char*)(base) + (off)))
 #define PA_STG(base, off, v) (*(double*)((char*)(base) + (off)) = (v))
-#define PA_STNT(base, off, v) __builtin_nontemporal_store((v), (double*)((char*)(base) + (off)))
-#define PA_STL(base, off, v) do { if (!(DBG & 1) || (v) == 1.2345e-300) { if (DBG & 2048) PA_STNT(base, off, v); else PA_STG(base, off, v); } } while (0)
 
-// DBG (diagnostic builds only, selected with PA_DBG): 256 = the first v3 schedule (requests at the top of a
-// step, stores spread over it; results correct); wrong results on purpose: 1 = no global stores in the
-// loop (a never-true data-dependent condition keeps the arithmetic alive), 2 = sqrt and divisions
-// replaced by additions, 4 = no x/y-neighbour reads from LDS (own values instead); correct results: 2048 = the output
-// stores carry the `nt` (non-temporal) bit: measured 2.00 against 1.92 ms per launch, so they do not.
-// PAIR: 16-byte stores.  A CU issues `global_store_dwordx2` at only ~7 B/cycle (measured: with 8-B
-// stores the sweep left the L2->HBM write interface idle -- TCC_EA0_WRREQ_STALL 0.5 M cycles against
-// 41 M for a no-arithmetic emulation of the same pattern -- while its time did not move with the
-// arithmetic, the LDS traffic or the prefetch depth).  Lanes 2m and 2m+1 therefore swap one value
-// (DPP quad_perm [1,0,3,2]) so that the even lane holds component A of cells 2m, 2m+1 and the odd
-// lane component B of the same two cells: one `global_store_dwordx4` writes 512 B of A and 512 B
-// of B, four store instructions per plane instead of eight.  Needs full 64-wide tiles, an even row
-// length and an even first column in the output FAB (checked on the host, else PAIR = false).
-__device__ __forceinline__ double swap_lane_pair(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
 typedef double pa_d2 __attribute__((ext_vector_type(2)));
-// lane parity `odd`; `off` = even lane: 8*lane, odd lane: 8*(lane-1) + component stride
-__device__ __forceinline__ void store_pair(char* base, unsigned off, bool odd, double A, double B) {
-  const double recv = swap_lane_pair(odd ? A : B);
-  pa_d2 v;
-  v.x = odd ? recv : A;
-  v.y = odd ? B : recv;
-  *(pa_d2*)(base + off) = v;
-}
 
 // CG: the progress variable in the ghost cells behind SPECIAL box faces (coarse-fine / wall) is not (phi_ghost - pmin) *
 // invdenom but the reference's boundary condition applied to c itself; with CG the kernel takes those values from the
@@ -135,15 +114,14 @@ template <int MTY>
 struct MarchLdsG {
   double gy[3][MTY + 2][PA_MLW], gz[3][MTY + 2][PA_MLW];  // (G_x rides in MarchLds::p, which a GOUT sweep does not use)
 };
-template <typename BP, int PA_MTY, bool CLIP, bool PAIR, int DBG, bool CG, int GOUT = 0>
+template <typename BP, int PA_MTY, bool CLIP, bool CG, int GOUT = 0>
 __device__ __forceinline__ void gradcurv_march3_body(const BP& bp, const MarchArgs& A, const unsigned bid_x, const unsigned bid_y) {
-  static_assert(!GOUT || (CG && !PAIR && DBG == 0), "GOUT: exact-normal sweep, 8-byte stores");
+  static_assert(!GOUT || CG, "GOUT: exact-normal sweep");
   constexpr bool KG = GOUT == 2;
   FabView P, O;
   DBox V;
   double dxinv[3];
   constexpr int PA_MROWS = PA_MTY + 2;
-  constexpr bool OLD_SCHED = (DBG & 256) != 0;  // requests at the top of a step + stores spread over it (first v3 schedule)
   unsigned bid = bid_x;
   int box;
   if (A.wgtab) {
@@ -299,10 +277,6 @@ __device__ __forceinline__ void gradcurv_march3_body(const BP& bp, const MarchAr
         __builtin_amdgcn_sched_barrier(0);
         gp += (p + 5 <= kfmax) ? pps : 0;
         go += (p + 4 + sh <= pend) ? pso : 0;
-        if (OLD_SCHED) {
-          f[SP] = PA_LDG(gp, lo8);
-          fo[SP] = PA_LDG(go, lo8);
-        }
         const double cl = S.c[SP][rr][xs - 1], cr = S.c[SP][rr][xs + 1];
         const double cin = S.c[SP][(rr == 0) ? 1 : rr - 1][xs];
         const double cs = (rr == 0) ? co : cin, cn = (rr == 0) ? cin : co;
@@ -317,11 +291,9 @@ __device__ __forceinline__ void gradcurv_march3_body(const BP& bp, const MarchAr
         if (!GOUT) S.p[SP][rr][xs] = p0;
         if constexpr (KG) { PA_SGX[SP][rr][xs] = ggx; SG.gy[SP][rr][xs] = ggy; SG.gz[SP][rr][xs] = ggz; }
         __syncthreads();
-        if (!OLD_SCHED) {
-          PA_OPAQUE(lo8);
-          f[SP] = PA_LDG(gp, lo8);
-          fo[SP] = PA_LDG(go, lo8);
-        }
+        PA_OPAQUE(lo8);
+        f[SP] = PA_LDG(gp, lo8);
+        fo[SP] = PA_LDG(go, lo8);
         cm = cc; cc = cp; cp = ysp ? xo : PA_PROG(x); co = (ymode == 2) ? xo : PA_PROG(xo);
         fzc = fzh;
         p0 = p1; p1 = x;
@@ -336,10 +308,7 @@ __device__ __forceinline__ void gradcurv_march3_body(const BP& bp, const MarchAr
     gp += 4 * pps;
     gp += (k0 + 3 <= kfmax) ? pps : 0;
     f[2] = PA_LDG(gp, lo8);  // gp -> plane min(k0+3, k1+2), the youngest plane requested
-    // Enter the loop with nothing in flight: one `s_waitcnt vmcnt(N)` must hold for the first trip and
-    // for the steady state, so requests still pending on entry (no stores behind them yet) would pull
-    // N down from 26 to 2 and drain the stores every third plane.  Costs one round trip per segment.
-    asm volatile("" ::"v"(f[0]), "v"(f[1]), "v"(f[2]));
+    // (no drain: the three requests stay in flight into the store-free warm-up steps below)
     // CG: c of the ghost plane behind a special z face from the face's compact array [y][x]
     double cgzv = 0.0;
     int pzh = -0x40000000;  // the step whose request becomes c of plane hi_z + 1
@@ -375,75 +344,52 @@ __device__ __forceinline__ void gradcurv_march3_body(const BP& bp, const MarchAr
       gsb = (gfl & 1) || ((gfl & 2) && i - V.lo[0] < 3) || ((gfl & 4) && V.hi[0] - i < 3) || (j - V.lo[1] < 3) || (V.hi[1] - j < 3);
     }
     const double thr = A.thr;
-    const bool odd = lane & 1;
-    unsigned lo16 = odd ? (unsigned)(le - 1) * 8u + (unsigned)osc : (unsigned)le * 8u;
     // normal at plane p, outputs at plane q = p-1.  The 8 results of a plane are kept in registers
-    // and stored at the top of the next step; the first three steps have nothing valid to store yet
-    // and write to plane k0, which the same thread overwrites in program order.
+    // and stored at the top of the next step.  Steps k0-1, k0, k0+1 (the warm-up: stc = false) have
+    // nothing valid to store yet and are compiled without the burst; step k0+2 is the first that
+    // stores (the results of plane k0), and from there on the output base advances a plane per step.
     double o0 = 0, o1 = 0, o2 = 0, o3 = 0, o4 = 0, o5 = 0, o6 = 0, o7 = 0;
-    auto step = [&](auto spc, int p) __attribute__((always_inline)) {
+    auto step_impl = [&](auto spc, int p, auto stc) __attribute__((always_inline)) {
       constexpr int SP = decltype(spc)::value, SP1 = (SP + 1) % 3, SQ = (SP + 2) % 3;
+      constexpr bool ST = decltype(stc)::value;
       double x;  // phi(min(p+2, k1+2)), requested three steps ago
       PA_TAKE(x, f[SP]);
       PA_OPAQUE(lo8);
       __builtin_amdgcn_sched_barrier(0);
       gp += (p + 5 <= kfmax) ? pps : 0;
-      if (OLD_SCHED) f[SP] = PA_LDG(gp, lo8);
-      if (!OLD_SCHED && !(DBG & 512)) {  // the 8 results of the previous plane, one burst; the request for plane p+5 follows the barrier
-        if (PAIR) {
-          PA_OPAQUE(lo16);
-          store_pair(ob, lo16, odd, o0, o1); store_pair(ob + 2 * osc, lo16, odd, o2, o3);
-          store_pair(ob + 4 * osc, lo16, odd, o4, o5); store_pair(ob + 6 * osc, lo16, odd, o6, o7);
-        } else if (GOUT) {
-          PA_STL(ob, lo8, o0); PA_STL(ob + osc, lo8, o1); PA_STL(ob + 2 * osc, lo8, o2); PA_STL(ob + 3 * osc, lo8, o3);
-          PA_STL(ob + 4 * osc, lo8, o4);
-          if constexpr (KG) PA_STL(ob + 5 * osc, lo8, o8);
-          if (gs) { PA_STL(ob2, lo8, o5); PA_STL(ob2 + osc2, lo8, o6); PA_STL(ob2 + 2 * osc2, lo8, o7); }
+      if constexpr (ST) {  // the 8 results of the previous plane, one burst; the request for plane p+5 follows the barrier
+        if (GOUT) {
+          PA_STG(ob, lo8, o0); PA_STG(ob + osc, lo8, o1); PA_STG(ob + 2 * osc, lo8, o2); PA_STG(ob + 3 * osc, lo8, o3);
+          PA_STG(ob + 4 * osc, lo8, o4);
+          if constexpr (KG) PA_STG(ob + 5 * osc, lo8, o8);
+          if (gs) { PA_STG(ob2, lo8, o5); PA_STG(ob2 + osc2, lo8, o6); PA_STG(ob2 + 2 * osc2, lo8, o7); }
         } else {
-          PA_STL(ob, lo8, o0); PA_STL(ob + osc, lo8, o1); PA_STL(ob + 2 * osc, lo8, o2); PA_STL(ob + 3 * osc, lo8, o3);
-          PA_STL(ob + 4 * osc, lo8, o4); PA_STL(ob + 5 * osc, lo8, o5); PA_STL(ob + 6 * osc, lo8, o6); PA_STL(ob + 7 * osc, lo8, o7);
+          PA_STG(ob, lo8, o0); PA_STG(ob + osc, lo8, o1); PA_STG(ob + 2 * osc, lo8, o2); PA_STG(ob + 3 * osc, lo8, o3);
+          PA_STG(ob + 4 * osc, lo8, o4); PA_STG(ob + 5 * osc, lo8, o5); PA_STG(ob + 6 * osc, lo8, o6); PA_STG(ob + 7 * osc, lo8, o7);
         }
         __builtin_amdgcn_sched_barrier(0);  // the burst stays ahead of the plane's arithmetic
       }
-      const double cl = (DBG & 4) ? cm : S.c[SP][rr][xs - 1], cr = (DBG & 4) ? cp : S.c[SP][rr][xs + 1];
-      const double cs = (DBG & 4) ? cm : S.c[SP][rr - 1][xs], cn = (DBG & 4) ? cp : S.c[SP][rr + 1][xs];
-      if (OLD_SCHED) { if (PAIR) { PA_OPAQUE(lo16); store_pair(ob, lo16, odd, o0, o1); } else PA_STL(ob, lo8, o0); }
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
+      const double cl = S.c[SP][rr][xs - 1], cr = S.c[SP][rr][xs + 1];
+      const double cs = S.c[SP][rr - 1][xs], cn = S.c[SP][rr + 1][xs];
       const double ggx = cdiff(dxinv[0], cl, cc, cr);
       const double ggy = cdiff(dxinv[1], cs, cc, cn);
       const double fzh = zflux(dxinv[2], cc, cp);
       const double ggz = favg(fzc, fzh);
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
-      if (OLD_SCHED && !PAIR) PA_STL(ob + osc, lo8, o1);
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
-      const double sn = (DBG & 2) ? (ggx * ggx + ggy * ggy + ggz * ggz) : sqrt(ggx * ggx + ggy * ggy + ggz * ggz);
+      const double sn = sqrt(ggx * ggx + ggy * ggy + ggz * ggz);
       const double ng = -((1e-14 < sn) ? sn : 1e-14);
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
-      if (OLD_SCHED) { if (PAIR) { PA_OPAQUE(lo16); store_pair(ob + 2 * osc, lo16, odd, o2, o3); } else PA_STL(ob + 2 * osc, lo8, o2); }
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
       double nxp, nyp, nzp;
-      if (DBG & 2) { nxp = ggx + ng; nyp = ggy + ng; nzp = ggz + ng; }
-      else div3_shared(ggx, ggy, ggz, ng, nxp, nyp, nzp);
+      div3_shared(ggx, ggy, ggz, ng, nxp, nyp, nzp);
       PA_OPAQUE(lo8);  // new basic block after the guard's branch: see PA_OPAQUE
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
-      if (OLD_SCHED && !PAIR) PA_STL(ob + 3 * osc, lo8, o3);
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
       S.ny[SP][rr][lane] = nyp;
       S.nx[SP][rr - 1][xs] = nxp;
       S.c[SP1][rr][xs] = cp;
       if (!GOUT) S.p[SP][rr][xs] = p0;
       if constexpr (KG) { PA_SGX[SP][rr][xs] = ggx; SG.gy[SP][rr][xs] = ggy; SG.gz[SP][rr][xs] = ggz; }
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
-      if (OLD_SCHED && !PAIR) PA_STL(ob + 4 * osc, lo8, o4);
-      if (DBG & 512) {  // experiment: the burst just before the barrier
-        PA_OPAQUE(lo8);
-        PA_STL(ob, lo8, o0); PA_STL(ob + osc, lo8, o1); PA_STL(ob + 2 * osc, lo8, o2); PA_STL(ob + 3 * osc, lo8, o3);
-        PA_STL(ob + 4 * osc, lo8, o4); PA_STL(ob + 5 * osc, lo8, o5); PA_STL(ob + 6 * osc, lo8, o6); PA_STL(ob + 7 * osc, lo8, o7);
-      }
       __syncthreads();
-      if (!OLD_SCHED && !(DBG & 1024)) { PA_OPAQUE(lo8); f[SP] = PA_LDG(gp, lo8); }  // request for plane p+5, after the barrier (see the header)
-      const double nxl = (DBG & 4) ? nzq : S.nx[SQ][rr - 1][xs - 1], nxr = (DBG & 4) ? nzp : S.nx[SQ][rr - 1][xs + 1];
-      const double nys = (DBG & 4) ? nzq : S.ny[SQ][rr - 1][lane], nyn = (DBG & 4) ? nzp : S.ny[SQ][rr + 1][lane];
+      PA_OPAQUE(lo8);
+      f[SP] = PA_LDG(gp, lo8);  // request for plane p+5, after the barrier (see the header)
+      const double nxl = S.nx[SQ][rr - 1][xs - 1], nxr = S.nx[SQ][rr - 1][xs + 1];
+      const double nys = S.ny[SQ][rr - 1][lane], nyn = S.ny[SQ][rr + 1][lane];
       const double fznh = zflux(dxinv[2], nzq, nzp);
       double curv = 0.0;
       curv += cdiff(dxinv[0], nxl, nxq, nxr);
@@ -473,29 +419,20 @@ __device__ __forceinline__ void gradcurv_march3_body(const BP& bp, const MarchAr
         }
         (void)xh;
       }
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
-      if (OLD_SCHED) { if (PAIR) { PA_OPAQUE(lo16); store_pair(ob + 4 * osc, lo16, odd, o4, o5); } else PA_STL(ob + 5 * osc, lo8, o5); }
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
       // phi gradient at plane q (pc = phi(q), p0 = phi(q+1); fzp = low z-face flux at plane q)
       double gx = 0, gy = 0, gz = 0, gm = 0, fzph = 0;
       if (!GOUT) {
-        const double pl = (DBG & 4) ? p1 : S.p[SQ][rr][xs - 1], pr = (DBG & 4) ? p0 : S.p[SQ][rr][xs + 1];
-        const double ps = (DBG & 4) ? p1 : S.p[SQ][rr - 1][xs], pnn = (DBG & 4) ? p0 : S.p[SQ][rr + 1][xs];
+        const double pl = S.p[SQ][rr][xs - 1], pr = S.p[SQ][rr][xs + 1];
+        const double ps = S.p[SQ][rr - 1][xs], pnn = S.p[SQ][rr + 1][xs];
         gx = cdiff(dxinv[0], pl, pc, pr);
         gy = cdiff(dxinv[1], ps, pc, pnn);
         fzph = zflux(dxinv[2], pc, p0);
         gz = favg(fzp, fzph);
       }
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
-      if (OLD_SCHED && !PAIR) PA_STL(ob + 6 * osc, lo8, o6);
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
-      if (!GOUT) gm = (DBG & 2) ? (gx * gx + gy * gy + gz * gz) : sqrt(gx * gx + gy * gy + gz * gz);
-      if (OLD_SCHED) __builtin_amdgcn_sched_barrier(0);
-      if (OLD_SCHED) { if (PAIR) { PA_OPAQUE(lo16); store_pair(ob + 6 * osc, lo16, odd, o6, o7); } else PA_STL(ob + 7 * osc, lo8, o7); }
-      if (DBG & 1024) { PA_OPAQUE(lo8); f[SP] = PA_LDG(gp, lo8); }  // experiment: the request at the end of the step
-      ob += (p >= k0 + 2) ? ops : 0;
+      if (!GOUT) gm = sqrt(gx * gx + gy * gy + gz * gz);
+      if constexpr (ST) ob += ops;
       if (GOUT) {  // [Progress K Nx Ny Nz] + G; cm = c at plane q; Progress and G are not clipped (curvature.cpp:557-566 clips K and N)
-        ob2 += (p >= k0 + 2) ? ops2 : 0;
+        if constexpr (ST) ob2 += ops2;
         const bool clip = CLIP && ((cm < thr) || (cm > 1.0 - thr));
         if constexpr (KG) {  // k_gauss_curv (pa_curvopts.hip) on plane q: x / y neighbours of G from the rings, z-neighbours from the registers
           double H[3][3];
@@ -551,14 +488,36 @@ __device__ __forceinline__ void gradcurv_march3_body(const BP& bp, const MarchAr
       pc = p0; p0 = p1; p1 = x;
       nxq = nxp; nyq = nyp; nzq = nzp;
     };
-    PA_RUN3(step)
+    auto step = [&](auto spc, int p) __attribute__((always_inline)) { step_impl(spc, p, std::true_type{}); };
+    auto stepw = [&](auto spc, int p) __attribute__((always_inline)) { step_impl(spc, p, std::false_type{}); };
+    {
+      // pend = k1 + 1 >= k0 + 1: the three warm-up steps always exist.  One group of three storing steps is peeled in
+      // front of the loop, so that the loop is entered with what its back edge carries -- the requests and bursts of
+      // the two steps before -- and one set of wait counts serves the first trip and the steady state.  The ring slot
+      // of step p stays (p - (k0 - 1)) mod 3, and every step keeps its one barrier (the other roles run PA_RUN3).
+      int p = k0 - 1;
+      stepw(I0{}, p);
+      stepw(I1{}, p + 1);
+      stepw(I2{}, p + 2);
+      p += 3;
+      if (p + 2 <= pend) {
+        step(I0{}, p);
+        step(I1{}, p + 1);
+        step(I2{}, p + 2);
+        p += 3;
+        _Pragma("unroll 1") for (; p + 2 <= pend; p += 3) {
+          step(I0{}, p);
+          step(I1{}, p + 1);
+          step(I2{}, p + 2);
+        }
+      }
+      if (p <= pend) {
+        step(I0{}, p);
+        if (p + 1 <= pend) step(I1{}, p + 1);
+      }
+    }
     // results of the last plane (k1)
-    if (PAIR) {
-      store_pair(ob, lo16, odd, o0, o1);
-      store_pair(ob + 2 * osc, lo16, odd, o2, o3);
-      store_pair(ob + 4 * osc, lo16, odd, o4, o5);
-      store_pair(ob + 6 * osc, lo16, odd, o6, o7);
-    } else if (GOUT) {
+    if (GOUT) {
       PA_STG(ob, lo8, o0);
       PA_STG(ob + osc, lo8, o1);
       PA_STG(ob + 2 * osc, lo8, o2);
@@ -683,10 +642,6 @@ __device__ __forceinline__ void gradcurv_march3_body(const BP& bp, const MarchAr
       gp += (p + 5 <= kfmax) ? pps : 0;
       go += (p + 4 <= pend) ? pps : 0;
       if (CG) gol += (p + 4 + sh <= pend) ? pso : 0;
-      if (OLD_SCHED) {
-        f[SP] = PA_LDG(gp, og);
-        fo[SP] = PA_LDO(0);
-      }
       const double inner = S.c[SP][rr][xin];
       const double cl = side ? inner : co, cr = side ? co : inner;
       const double cs = S.c[SP][rlo][xs], cn = S.c[SP][rhi][xs];
@@ -702,12 +657,10 @@ __device__ __forceinline__ void gradcurv_march3_body(const BP& bp, const MarchAr
       if (!GOUT) S.p[SP][rr][xs] = p0;
       if constexpr (KG) { PA_SGX[SP][rr][xs] = ggx; SG.gy[SP][rr][xs] = ggy; SG.gz[SP][rr][xs] = ggz; }
       __syncthreads();
-      if (!OLD_SCHED) {
-        PA_OPAQUE(og);
-        if (!CG) PA_OPAQUE(oo);
-        f[SP] = PA_LDG(gp, og);
-        fo[SP] = PA_LDO(0);
-      }
+      PA_OPAQUE(og);
+      if (!CG) PA_OPAQUE(oo);
+      f[SP] = PA_LDG(gp, og);
+      fo[SP] = PA_LDO(0);
       if (NCGF) ncg_store(p - 2, (p - 1) & 1);  // the row waves handed plane p - 2 over after the PREVIOUS barrier
       cm = cc; cc = cp; cp = xsp ? xo : PA_PROG(x); co = (xmode == 2) ? xo : PA_PROG(xo);
       fzc = fzh;
@@ -729,9 +682,9 @@ __device__ __forceinline__ void gradcurv_march3_body(const BP& bp, const MarchAr
 #undef PA_SGX
 }
 
-template <typename BP, int PA_MTY, bool CLIP, bool PAIR = false, int DBG = 0, bool CG = false>
+template <typename BP, int PA_MTY, bool CLIP, bool CG = false>
 __global__ __launch_bounds__(64 * (PA_MTY + 3), 1) void k_gradcurv_march3(BP bp, MarchArgs A) {
-  gradcurv_march3_body<BP, PA_MTY, CLIP, PAIR, DBG, CG>(bp, A, blockIdx.x, blockIdx.y);
+  gradcurv_march3_body<BP, PA_MTY, CLIP, CG>(bp, A, blockIdx.x, blockIdx.y);
 }
 
 // The CG sweeps of several levels in ONE launch (exact-normal pipeline: the sweeps of different levels do not depend on
@@ -767,11 +720,11 @@ __global__ __launch_bounds__(64 * (PA_MTY + 3), 1) void k_gradcurv_march3_levels
   int l = 0;
   while (l + 1 < S.n && blockIdx.x >= S.wg0[l + 1]) ++l;
   if (GOUT || (gridDim.y == 1 && !S.prog)) {  // one component: the arguments straight from the argument segment
-    gradcurv_march3_body<LevelBP2, PA_MTY, CLIP, false, 0, true, GOUT>(S.bp[l], S.A[l], blockIdx.x - S.wg0[l], 0u);
+    gradcurv_march3_body<LevelBP2, PA_MTY, CLIP, true, GOUT>(S.bp[l], S.A[l], blockIdx.x - S.wg0[l], 0u);
     return;
   }
   LevelBP2 bp;
   MarchArgs A;
   sweep_slot(S, l, bp, A);
-  gradcurv_march3_body<LevelBP2, PA_MTY, CLIP, false, 0, true, GOUT>(bp, A, blockIdx.x - S.wg0[l], 0u);
+  gradcurv_march3_body<LevelBP2, PA_MTY, CLIP, true, GOUT>(bp, A, blockIdx.x - S.wg0[l], 0u);
 }

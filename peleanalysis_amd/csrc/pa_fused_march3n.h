@@ -120,7 +120,6 @@ __device__ __forceinline__ void gradcurv_march3n_body(const BP& bp, const MarchA
     gp += 4 * pps;
     gp += (k0 + 3 <= kfmax) ? pps : 0;
     f[2] = PA_LDG(gp, lo8);
-    asm volatile("" ::"v"(f[0]), "v"(f[1]), "v"(f[2]));  // enter the loop with nothing in flight (see pa_fused_march3.h)
     double cgzv = 0.0;
     int pzh = -0x40000000;  // the step whose request becomes c of plane hi_z + 1
     if (CG && cgzl) {
@@ -150,22 +149,26 @@ __device__ __forceinline__ void gradcurv_march3n_body(const BP& bp, const MarchA
     double gxq = 0, gyq = 0, gzq = 0;  // GOUT: G of plane q
     const double thr = A.thr;
     double o0 = 0, o1 = 0, o2 = 0, o3 = 0, o4 = 0, o5 = 0, o6 = 0, o7 = 0;
-    auto step = [&](auto spc, int p) __attribute__((always_inline)) {
+    // the warm-up steps k0-1, k0, k0+1 (stc = false) have nothing to store and carry no burst: see pa_fused_march3.h
+    auto step_impl = [&](auto spc, int p, auto stc) __attribute__((always_inline)) {
       constexpr int SP = decltype(spc)::value, SP1 = (SP + 1) % 3, SQ = (SP + 2) % 3;
+      constexpr bool ST = decltype(stc)::value;
       double x;
       PA_TAKE(x, f[SP]);
       PA_OPAQUE(so8);
       __builtin_amdgcn_sched_barrier(0);
       gp += (p + 5 <= kfmax) ? pps : 0;
-      PA_STG(ob, so8, o0); PA_STG(ob + osc, so8, o1); PA_STG(ob + 2 * osc, so8, o2); PA_STG(ob + 3 * osc, so8, o3);
-      PA_STG(ob + 4 * osc, so8, o4);
-      if (GOUT) {
-        PA_OPAQUE(sg8);
-        PA_STG(ob2, sg8, o5); PA_STG(ob2 + osc2, sg8, o6); PA_STG(ob2 + 2 * osc2, sg8, o7);
-      } else {
-        PA_STG(ob + 5 * osc, so8, o5); PA_STG(ob + 6 * osc, so8, o6); PA_STG(ob + 7 * osc, so8, o7);
+      if constexpr (ST) {
+        PA_STG(ob, so8, o0); PA_STG(ob + osc, so8, o1); PA_STG(ob + 2 * osc, so8, o2); PA_STG(ob + 3 * osc, so8, o3);
+        PA_STG(ob + 4 * osc, so8, o4);
+        if (GOUT) {
+          PA_OPAQUE(sg8);
+          PA_STG(ob2, sg8, o5); PA_STG(ob2 + osc2, sg8, o6); PA_STG(ob2 + 2 * osc2, sg8, o7);
+        } else {
+          PA_STG(ob + 5 * osc, so8, o5); PA_STG(ob + 6 * osc, so8, o6); PA_STG(ob + 7 * osc, so8, o7);
+        }
+        __builtin_amdgcn_sched_barrier(0);
       }
-      __builtin_amdgcn_sched_barrier(0);
       const double cl = S.c[SP][rr][xs - 1], cr = S.c[SP][rr][xs + 1];
       const double cs = S.c[SP][rr - 1][xs], cn = S.c[SP][rr + 1][xs];
       const double ggx = cdiff(dxinv[0], cl, cc, cr);
@@ -201,9 +204,9 @@ __device__ __forceinline__ void gradcurv_march3n_body(const BP& bp, const MarchA
         gz = favg(fzp, fzph);
         gm = sqrt(gx * gx + gy * gy + gz * gz);
       }
-      ob += (p >= k0 + 2) ? ops : 0;
+      if constexpr (ST) ob += ops;
       if (GOUT) {  // [Progress K Nx Ny Nz] + G; cm = c at plane q; Progress and G are not clipped
-        ob2 += (p >= k0 + 2) ? ops2 : 0;
+        if constexpr (ST) ob2 += ops2;
         const bool clip = CLIP && ((cm < thr) || (cm > 1.0 - thr));
         o0 = cm;
         o1 = clip ? 0.0 : curv;
@@ -230,7 +233,30 @@ __device__ __forceinline__ void gradcurv_march3n_body(const BP& bp, const MarchA
       pc = p0; p0 = p1; p1 = x;
       nxq = nxp; nyq = nyp; nzq = nzp;
     };
-    PA_RUN3(step)
+    auto step = [&](auto spc, int p) __attribute__((always_inline)) { step_impl(spc, p, std::true_type{}); };
+    auto stepw = [&](auto spc, int p) __attribute__((always_inline)) { step_impl(spc, p, std::false_type{}); };
+    {  // warm-up, one peeled group of storing steps, the loop, the remainder (pa_fused_march3.h)
+      int p = k0 - 1;
+      stepw(I0{}, p);
+      stepw(I1{}, p + 1);
+      stepw(I2{}, p + 2);
+      p += 3;
+      if (p + 2 <= pend) {
+        step(I0{}, p);
+        step(I1{}, p + 1);
+        step(I2{}, p + 2);
+        p += 3;
+        _Pragma("unroll 1") for (; p + 2 <= pend; p += 3) {
+          step(I0{}, p);
+          step(I1{}, p + 1);
+          step(I2{}, p + 2);
+        }
+      }
+      if (p <= pend) {
+        step(I0{}, p);
+        if (p + 1 <= pend) step(I1{}, p + 1);
+      }
+    }
     PA_STG(ob, so8, o0); PA_STG(ob + osc, so8, o1); PA_STG(ob + 2 * osc, so8, o2); PA_STG(ob + 3 * osc, so8, o3);
     PA_STG(ob + 4 * osc, so8, o4);
     if (GOUT) {

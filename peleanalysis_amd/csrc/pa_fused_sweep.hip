@@ -17,7 +17,8 @@
 #include "pa_fused_march3n.h"
 #include <cstdlib>
 
-// planes per workgroup: 64 vs 128 measured 1.91 vs 1.94 ms with the burst schedule (within noise; more, shorter workgroups).  The tile
+// planes per workgroup: 64 vs 128 measured 1.91 vs 1.94 ms with the burst schedule (within noise; more, shorter workgroups; not
+// re-measured after round 11 took the junk stores and the drain out of a segment's prologue).  The tile
 // heights (13 / 8 / 4 rows by the boxes' height), the XCD-aware workgroup order (2) and 8-byte stores are what the measurements of
 // rounds 1-5 left standing; the 16-byte paired stores, the first marching kernel, tiles of 9-12 rows and the diagnostic builds of the
 // sweep went with their switches in round 6 (DESIGN_HISTORY.md lists what each measured).
@@ -73,8 +74,8 @@ static void march_launch(hipStream_t st, const BP& bp, int nx, int ny, int nz, u
     A.tiles_max = (int)g.x;
     g = dim3(g.x * 8u * ((nboxes + 7u) / 8u), 1);
     if (kname) *kname = "k_gradcurv_march3<MTY=" + std::to_string(M) + ",CLIP=" + std::to_string((int)clip) + ",PAIR=0,CG=" + std::to_string((int)(A.cg != 0)) + ">";
-    if (A.cg && !clip) hipLaunchKernelGGL((k_gradcurv_march3<BP, M, false, false, 0, true>), g, dim3(64 * (M + 3)), 0, st, bp, A);
-    else if (A.cg) hipLaunchKernelGGL((k_gradcurv_march3<BP, M, true, false, 0, true>), g, dim3(64 * (M + 3)), 0, st, bp, A);
+    if (A.cg && !clip) hipLaunchKernelGGL((k_gradcurv_march3<BP, M, false, true>), g, dim3(64 * (M + 3)), 0, st, bp, A);
+    else if (A.cg) hipLaunchKernelGGL((k_gradcurv_march3<BP, M, true, true>), g, dim3(64 * (M + 3)), 0, st, bp, A);
     else if (clip) hipLaunchKernelGGL((k_gradcurv_march3<BP, M, true>), g, dim3(64 * (M + 3)), 0, st, bp, A);
     else hipLaunchKernelGGL((k_gradcurv_march3<BP, M, false>), g, dim3(64 * (M + 3)), 0, st, bp, A);
   };

@@ -100,7 +100,7 @@ __device__ __forceinline__ void grad_march_body(const BP& bp, const GradMarchArg
     f[1] = PA_LDG(gp, lo8);
     gp += (k0 + 3 <= kf) ? pps : 0;
     f[2] = PA_LDG(gp, lo8);  // gp -> plane min(k0+3, k1+1), the youngest plane requested
-    asm volatile("" ::"v"(f[0]), "v"(f[1]), "v"(f[2]));  // enter the loop with nothing in flight (pa_fused_march3.h)
+    asm volatile("" ::"v"(f[0]), "v"(f[1]), "v"(f[2]));  // enter the loop with nothing in flight: one wait count must hold on its entry edge and its back edge
     S.p[0][rr][xs] = pc;
     __syncthreads();
     if (rr == 0 || rr == rtop) {  // y-halo rows: supply neighbours only
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(64 * (NRW + 2)) void k_grad_marchn(BP bp, GradMarch
     f[1] = PA_LDG(gp, lo8);
     gp += (k0 + 3 <= kf) ? pps : 0;
     f[2] = PA_LDG(gp, lo8);
-    asm volatile("" ::"v"(f[0]), "v"(f[1]), "v"(f[2]));  // enter the loop with nothing in flight (pa_fused_march3.h)
+    asm volatile("" ::"v"(f[0]), "v"(f[1]), "v"(f[2]));  // enter the loop with nothing in flight: one wait count must hold on its entry edge and its back edge
     S.p[0][rr][xs] = pc;
     __syncthreads();
     double fz = zflux(dxinv[2], pm, pc);
