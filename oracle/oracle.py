@@ -382,16 +382,24 @@ def sdf_level_set(tris, verts, origin, dx, n, exact_band=1, want_closest=False):
 
 
 _REF = {}
+REF_ROOT = "/root/reference"  # the reference tree, where a machine has it (tests patch this to hide it)
+REF_DIR = os.path.join(_HERE, "_ref")  # what `make ref` built from it (tests patch this to move it aside)
+
+
+def _ref_lib(name, need):
+    """oracle/_ref/<name>, built by `make ref` where the reference tree holds `need`; None where neither exists"""
+    key = (REF_DIR, REF_ROOT, name)
+    if key not in _REF:
+        path = os.path.join(REF_DIR, name)
+        if not os.path.exists(path) and REF_DIR == os.path.join(_HERE, "_ref") and os.path.exists(os.path.join(REF_ROOT, need)):
+            subprocess.call(["make", "-C", _HERE, "-s", "ref"])
+        _REF[key] = C.CDLL(path) if os.path.exists(path) else None
+    return _REF[key]
 
 
 def sdf_ref_lib():
     """The reference's own make_level_set3 compiled from /root/reference (oracle/_ref), or None."""
-    if "sdf" not in _REF:
-        path = os.path.join(_HERE, "_ref", "libsdfgen_ref.so")
-        if not os.path.exists(path) and os.path.isdir("/root/reference/Tools/SDFGen"):
-            subprocess.call(["make", "-C", _HERE, "-s", "ref"])
-        _REF["sdf"] = C.CDLL(path) if os.path.exists(path) else None
-    return _REF["sdf"]
+    return _ref_lib("libsdfgen_ref.so", "Tools/SDFGen")
 
 
 def sdf_level_set_ref(tris, verts, origin, dx, n, exact_band=1):
@@ -403,6 +411,82 @@ def sdf_level_set_ref(tris, verts, origin, dx, n, exact_band=1):
                                fdx, ni, nj, nk, phi.ctypes.data_as(C.c_void_p), int(exact_band))
     assert rc == 0
     return phi
+
+
+# ---------------------------------------------------------------- the reference's own isosurface arithmetic (oracle/_ref)
+REF_UNDEFINED = "undefined in the reference"  # iso_merge_ref: nodeSet.find(n) returned end() (isosurface.cpp:1699)
+REF_INCONSISTENT = "reference node set inconsistent"  # iso_merge_ref: the finished nodeSet holds two nodes its own ordering calls equal
+
+
+def iso_ref_lib(dim):
+    """Src/isosurface.cpp from Edge through Element, cut out and compiled with AMREX_SPACEDIM = dim by `make -C oracle ref`
+    (oracle/ref/iso_ref_wrap.cpp around it), or None where neither /root/reference nor a built oracle/_ref exists."""
+    assert dim in (2, 3)
+    return _ref_lib("libiso_ref%d.so" % dim, "Src/isosurface.cpp")
+
+
+def _fab_ref(dim, state, mask, slo, shi, isocomp, isoval, llo, lhi):
+    R = iso_ref_lib(dim)
+    if R is None:
+        return None
+    state = np.ascontiguousarray(state, dtype=np.float64)
+    mask = np.ascontiguousarray(mask, dtype=np.float64)
+    ncomp = state.shape[0]
+    assert state.ndim == dim + 1 and mask.shape == state.shape[1:] == tuple(int(h) - int(l) + 1 for l, h in zip(slo[:dim], shi[:dim]))[::-1]
+    iv = lambda v: (C.c_int32 * dim)(*[int(x) for x in v[:dim]])
+    fn = R.ref_mc_fab if dim == 3 else R.ref_msq_fab
+    nv, ne = C.c_int64(0), C.c_int64(0)
+    args = (state.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p), iv(slo), iv(shi), ncomp, int(isocomp), C.c_double(isoval), iv(llo), iv(lhi))
+    ncell = int(np.prod([max(int(h) - int(l) + 1, 0) for l, h in zip(llo[:dim], lhi[:dim])]))
+    max_v, max_e = dim * mask.size, (5 if dim == 3 else 2) * ncell  # one vertex per grid edge, 5 triangles (2 segments) per cell at the most
+    verts = np.zeros((max(max_v, 1), ncomp))
+    keys = np.zeros((max(max_v, 1), 2 * dim), dtype=np.int32)
+    elts = np.zeros((max(max_e, 1), dim), dtype=np.int32)
+    rc = fn(*args, verts.ctypes.data_as(C.c_void_p), keys.ctypes.data_as(C.c_void_p), C.c_int64(max_v), elts.ctypes.data_as(C.c_void_p),
+            C.c_int64(max_e), C.byref(nv), C.byref(ne))
+    assert rc == 0, "loop box leaves the FAB"
+    assert nv.value <= max_v and ne.value <= max_e
+    return verts[:nv.value].copy(), keys[:nv.value].copy(), elts[:ne.value].copy()
+
+
+def mc_fab_ref(state, mask, slo, shi, isocomp, isoval, llo, lhi):
+    """mc_fab's arguments and results, from the reference's compiled Polygonise / VertexInterp (per-FAB loop of
+    isosurface.cpp:1572-1592, ids as at :1601-1611); None without the reference libraries."""
+    return _fab_ref(3, state, mask, slo, shi, isocomp, isoval, llo, lhi)
+
+
+def msq_fab_ref(state, mask, lo, hi, isocomp, isoval, llo, lhi):
+    """msq_fab's arguments and results, from the reference's compiled Segmentise (AMREX_SPACEDIM == 2); None without the
+    reference libraries."""
+    return _fab_ref(2, state, mask, lo, hi, isocomp, isoval, llo, lhi)
+
+
+def iso_merge_ref(fragments, ncomp, dim=3, keep_inconsistent=False):
+    """iso_merge's arguments and results over the reference's own std::set<Node> and std::set<Element> (isosurface.cpp:1687-1726,
+    1751-1807).  None without the reference libraries.  Node::operator< is not a strict weak ordering, which std::set requires; two
+    outcomes show it, and they are reported apart:
+      REF_UNDEFINED     nodeSet.find(n) (:1699) returned end(), which the reference goes on to dereference: it has no result
+      REF_INCONSISTENT  (a check of OURS, not the reference's) the reference ran through and returned an answer, but its finished set
+                        holds two nodes that its own ordering calls the same -- which copies survive depends on the shape of the
+                        tree.  keep_inconsistent=True returns that answer (nodes, elts) all the same; the oracle deliberately
+                        does not reproduce it (quirk Q10: first copy kept)."""
+    R = iso_ref_lib(dim)
+    if R is None:
+        return None
+    nv = np.array([len(v) for v, _ in fragments], dtype=np.int64)
+    ne = np.array([len(t) for _, t in fragments], dtype=np.int64)
+    V = np.ascontiguousarray(np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1, ncomp) for v, _ in fragments] + [np.zeros((0, ncomp))]))
+    T = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.int32).reshape(-1, dim) for _, t in fragments] + [np.zeros((0, dim), np.int32)]))
+    nodes, elts = np.zeros((max(len(V), 1), ncomp)), np.zeros((max(len(T), 1), dim), dtype=np.int32)
+    nn, nel = C.c_int64(0), C.c_int64(0)
+    rc = R.ref_iso_merge(C.c_int64(len(fragments)), nv.ctypes.data_as(C.c_void_p), ne.ctypes.data_as(C.c_void_p), V.ctypes.data_as(C.c_void_p),
+                         T.ctypes.data_as(C.c_void_p), int(ncomp), nodes.ctypes.data_as(C.c_void_p), C.byref(nn), elts.ctypes.data_as(C.c_void_p), C.byref(nel))
+    if rc == 3:
+        return REF_UNDEFINED
+    if rc == 4 and not keep_inconsistent:
+        return REF_INCONSISTENT
+    assert rc in (0, 4)
+    return nodes[:nn.value], elts[:nel.value]
 
 
 # ---------------------------------------------------------------- do_smooth (curvature.cpp:328-406)
@@ -494,7 +578,13 @@ def iso_merge(fragments, ncomp):
     copies of a vertex that two FABs interpolated from opposite ends of the same edge; quirk Q10: a
     spatial hash replaces the not-quite-strict-weak std::set ordering, the FIRST inserted copy is
     kept); ids = order of first insertion; elements are rotated so the smallest id comes first,
-    degenerate ones dropped, then sorted (std::set<Element>)."""
+    degenerate ones dropped, then sorted (std::set<Element>).
+    Q10 is THIS PROJECT'S rule, not parity: where nodes within the tolerance of each other sit on opposite sides of third
+    nodes in the std::set's ordering, the reference's own nodeSet.find(n) (:1699) returns end() and is dereferenced (it has
+    no result: iso_merge_ref returns REF_UNDEFINED), or its insert walks past the copy it should have met and the set keeps
+    both (REF_INCONSISTENT: the compiled reference returns an answer with MORE nodes than this function, which this function
+    deliberately does not reproduce; tests/test_mc_oracle.py).  On every other input this function is pinned to the
+    reference's compiled code (tests/golden/mc_ref.npz)."""
     EPS, H = 1.0e-15, 1.0e-14
     grid = {}
     nodes = []
@@ -638,7 +728,8 @@ def isosurface_pipeline(levels, fields, comps, isocomp_index, isoval, MF, ngrow=
 # --------------------------------------------------------------------------------- 2-D isosurface (AMREX_SPACEDIM == 2)
 # Pure-Python restatement (small cases only) of Segmentise (isosurface.cpp:303-406), VertexInterp / VI_doIt (:257-301),
 # the per-FAB loop (:1574-1582), the node / element sets (:1687-1716, Element :886-927) and MakeCLines (:1159-1265).
-# PARITY UNPINNED: no 2-D golden data exists in the reference tree.
+# PINNED (msq_fab, iso2d_merge): Segmentise and the node / element sets compiled from the reference with AMREX_SPACEDIM == 2
+# (iso_ref_lib(2); tests/golden/mc_ref.npz, tests/test_mc_oracle.py).  MakeCLines lives in main(): PARITY UNPINNED.
 _SEG_CASES = {1: (0, 3), 14: (0, 3), 2: (0, 1), 13: (0, 1), 3: (1, 3), 12: (1, 3), 4: (1, 2), 11: (1, 2), 6: (0, 2), 9: (0, 2), 7: (2, 3), 8: (2, 3),
               5: (0, 1, 2, 3), 10: (0, 1, 2, 3)}
 

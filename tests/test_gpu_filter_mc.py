@@ -123,24 +123,7 @@ def test_filter_wide_windows(ctx, oracle, filter_mode, fgr):
 
 
 # ------------------------------------------------------------------------------- marching cubes
-def _mc_case(n, seed, masked):
-    """state FAB over box (-1..n)^3 with 3 coordinate comps + 2 fields; iso field = wrinkled sphere"""
-    lo, hi = np.array([-1, -1, -1]), np.array([n, n, n])
-    ax = (np.arange(lo[0], hi[0] + 1) + 0.5) / n
-    X, Y, Z = ax[None, None, :] + 0 * ax[:, None, None], ax[None, :, None] + 0 * ax[:, None, None], ax[:, None, None] + 0 * ax[None, None, :]
-    X, Y, Z = np.broadcast_arrays(X, Y, Z)
-    rng = np.random.default_rng(seed)
-    r = np.sqrt((X - 0.5) ** 2 + (Y - 0.47) ** 2 + (Z - 0.52) ** 2)
-    f = 1000.0 + 900.0 * np.tanh((r - 0.31) / 0.05) + 5.0 * rng.standard_normal(X.shape)
-    g = np.sin(3 * X) * np.cos(2 * Y) + Z
-    state = np.ascontiguousarray(np.stack([X, Y, Z, f, g]))
-    mask = np.ones(X.shape)
-    if masked:
-        mask[n // 2:, n // 3: 2 * n // 3, : n // 2] = -1.0  # "covered by a finer level"
-    # a few exact hits of the iso value and equal neighbours (eps branches of VI_doIt)
-    state[3, 3, 4, 5] = 1090.0
-    state[3, 7, 7, 7] = state[3, 7, 7, 8]
-    return lo, hi, state, mask
+from mc_cases import mc_case as _mc_case, ratio4_hierarchy as _ratio4_hierarchy, synthetic_cluster_fragments  # shared with tests/test_mc_oracle.py, tests/test_gpu_mc_ref.py
 
 
 @pytest.mark.parametrize("n,masked", [(12, False), (20, True), (33, True)])
@@ -337,34 +320,8 @@ def test_iso_merge_synthetic_clusters(ctx, oracle):
     nodes on and next to the faces of the 1e-14 hash cells (the neighbour probes), an element that collapses once its nodes
     merge, the same element arriving from two fragments in two rotations; then a chain a ~ b ~ c with a !~ c, which the
     device path must hand back (code 2) instead of guessing"""
-    rng = np.random.default_rng(17)
     nc = 5
-    base = np.concatenate([rng.random((400, 3)), 0.25 + 1.0e-14 * rng.integers(0, 50, (60, 3)), 0.5 + 1.0e-14 * rng.integers(0, 4, (60, 3)) + rng.choice([0.0, 1e-16, -1e-16], (60, 3))])
-    base = np.unique(base, axis=0)
-    rng.shuffle(base)
-
-    def data(p):  # node data is carried along from the FIRST copy: make the copies distinguishable
-        return np.concatenate([p, rng.random((len(p), nc - 3))], axis=1)
-
-    frags = []
-    n0 = len(base)
-    t0 = rng.integers(0, n0, (900, 3)).astype(np.int32)
-    frags.append((data(base), t0))
-    for rep in range(3):
-        pick = rng.choice(n0, 150, replace=False)
-        p = base[pick].copy()
-        ulps = rng.integers(-3, 4, p.shape)
-        for _ in range(3):
-            p = np.where(ulps > 0, np.nextafter(p, 2.0), np.where(ulps < 0, np.nextafter(p, -1.0), p))
-            ulps = ulps - np.sign(ulps)
-        extra = rng.random((40, 3))
-        pts = np.concatenate([p, extra])
-        rng.shuffle(pts)
-        t = rng.integers(0, len(pts), (500, 3)).astype(np.int32)
-        frags.append((data(pts), t))
-    # the first fragment's elements again, rotated, through a fragment that holds exact copies of its nodes
-    frags.append((data(base), np.roll(t0[:200], 1, axis=1)))
-    frags.append((np.zeros((0, nc)), np.zeros((0, 3), np.int32)))
+    frags, data = synthetic_cluster_fragments(nc)
     wn, we = oracle.iso_merge(frags, nc)
     got = capi.iso_merge(ctx, frags, nc)
     assert got is not None
@@ -564,14 +521,6 @@ def test_marching_cubes_hierarchy_call_matches_oracle_and_level_calls(ctx, oracl
             c5.close()
     got = capi.mc_hierarchy(ctx, dst, fm, loops, 3, 1.0e30)
     assert all(len(t) == 0 and len(v) == 0 for lev in got for (v, _, t) in lev)
-
-
-def _ratio4_hierarchy(per):
-    """2 levels, refinement ratio 4: base 24^3 in 12^3 boxes; level 1 = coarse cells [6, 15] x [6, 17] x [8, 15] refined (x4) in boxes <= 24"""
-    from peleanalysis_amd.hierarchy import Hierarchy, Level, chop_box
-    l0 = Level(chop_box((0, 0, 0), (23, 23, 23), 12), (0, 0, 0), (23, 23, 23), per, np.zeros(3), np.ones(3))
-    l1 = Level(chop_box((24, 24, 32), (63, 71, 63), 24), (0, 0, 0), (95, 95, 95), per, np.zeros(3), np.ones(3))
-    return Hierarchy([l0, l1], 4)
 
 
 @pytest.mark.parametrize("interp,ng", [(0, 1), (1, 2), (1, 4), (0, 3)])

@@ -4,6 +4,11 @@
 //            (Euclidean) are one node, the FIRST inserted copy is kept, id = insertion order
 //   elements node-id triples rotated so the smallest id comes first (orientation preserved),
 //            degenerate ones dropped, unique, sorted lexicographically (std::set<Element> order)
+// Held bit for bit to the reference's compiled std::set<Node> / std::set<Element> on inputs where the reference's node set is
+// consistent (tests/test_mc_oracle.py, tests/golden/mc_ref.npz).  "First copy kept" is THIS PROJECT'S rule where it is not:
+// Node::operator< is no strict weak ordering, and on clusters of nodes within the tolerance of each other the reference's own
+// nodeSet.find (:1699) returns end() and is dereferenced, or its set keeps copies it calls equal and it returns more nodes than
+// this class does.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -53,7 +58,12 @@ class IsoMerger {
   std::vector<double> nodes_;
   std::vector<std::array<int32_t, 3>> elts_;
   struct Key { long long x, y, z; bool operator==(const Key& o) const { return x == o.x && y == o.y && z == o.z; } };
-  struct KeyHash { size_t operator()(const Key& k) const { return (size_t)(k.x * 73856093LL ^ k.y * 19349663LL ^ k.z * 83492791LL); } };
+  // unsigned products: a coordinate of 0.4 is hash cell 4e13, and 4e13 * 73856093 overflows a signed 64-bit integer (undefined)
+  struct KeyHash {
+    size_t operator()(const Key& k) const {
+      return (size_t)((uint64_t)k.x * 73856093ULL ^ (uint64_t)k.y * 19349663ULL ^ (uint64_t)k.z * 83492791ULL);
+    }
+  };
   std::unordered_map<Key, std::vector<int32_t>, KeyHash> grid_;
 
   int32_t node_id(const double* p) {
