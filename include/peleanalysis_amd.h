@@ -785,6 +785,37 @@ int pa_gradcurv_run_comps2(pa_ctx*, int nlev, pa_mf* const* state, int comp0, in
                            const pa_curv_params*, pa_mf* const* work, pa_mf* const* out, int ocomp, int nbatch,
                            int (*done)(void* user, int comp, int ocomp), void* user);
 
+/* ------------------------------------------------- resampling onto a foreign BoxArray + running sum (avgPlotfiles.cpp)
+ * One object (pa_resample) lives across the files of an average.  The caller owns the multifabs: per output level l a running
+ * multifab on the output BoxArray U_l (avgPlotfiles.cpp:157-167) and, for every level but the finest, a work multifab T_l on the
+ * same pa_level with g_l ghost layers, g = 0 on the finest level and one more per level down (with interp_type 0 none are needed).
+ * For file f and level l, V(f, l) is defined over the whole level-l domain: the file's own value where one of its level-l boxes
+ * holds the cell, elsewhere -- also when the file has no level l -- the interpolant of V(f, l-1): interp_type 0 the parent,
+ * 1 the cell-conservative linear rule of pa_fillpatch_two_levels (same operations, same operands; coarse neighbours beyond a wall
+ * are the nearest cell inside, beyond a periodic face the wrapped one; periodicity is the output level's is_per).  This is
+ * FillPatchTwoLevels of the file's levels l-1, l wherever the parent's 27 neighbours are data of the file's level l-1 (properly
+ * nested files) and its recursive extension elsewhere (PltFileManager::fillPatchFromPlt is recalled, not restated: DESIGN.md 1).
+ * The output is (((0.0 + V(1,l)) + V(2,l)) + ... + V(nf,l)) * (1.0 / nf) in call order, each cell summed by one thread: the bits
+ * do not depend on the tiling of U_l, the order of the file's boxes or how the variables are split into passes.
+ * One rank; 3-D levels; ratio 2 or 4.  add_file_level is asynchronous on the context's stream; finish is synchronous. */
+typedef struct pa_resample pa_resample;
+pa_resample* pa_resample_create(pa_ctx*);
+/* running_data[lev].define + setVal(0.0) (avgPlotfiles.cpp:156-167): the nlev running multifabs (coarsest first, at least nvar
+ * components each, 1 <= nvar <= 16; the first nvar components are zeroed) of one pass over the files; clears the counter */
+int pa_resample_begin(pa_ctx*, pa_resample*, int nlev, pa_mf* const* running, int nvar);
+/* fillPatchFromPlt + MultiFab::Add for one file and level (avgPlotfiles.cpp:178-186), levels coarse first within a file: the valid
+ * cells of V(f, lev) are added to running[lev]; work (NULL: not needed by a finer level) receives V(f, lev) in its valid and
+ * ghost cells.  file: the file's level-lev data on its own pa_level (same domain; NULL: the file has no such level); comp_map[v] =
+ * component of `file` that holds variable v (variables= resolved per file, :101-115, :183).  crse_work: work of level lev - 1
+ * filled by the previous call for this file (NULL on level 0), with at least ceil(g / ratio) + interp_type ghost layers. */
+int pa_resample_add_file_level(pa_ctx*, pa_resample*, int lev, const pa_mf* file, const int32_t* comp_map, const pa_mf* crse_work,
+                               int ratio, int interp_type, pa_mf* work);
+/* running_data[lev].mult(1.0 / nf) (avgPlotfiles.cpp:191-195) on every level; waits; nosrc (may be NULL) = cells, ghost cells of the
+ * work multifabs included, for which neither the file nor the coarser work multifab had data (they hold NaN): 0 whenever the
+ * file's level 0 covers the domain and the output levels are nested */
+int pa_resample_finish(pa_ctx*, pa_resample*, int nfiles, int64_t* nosrc);
+void pa_resample_destroy(pa_resample*);
+
 #ifdef __cplusplus
 }
 #endif

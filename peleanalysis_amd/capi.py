@@ -239,6 +239,11 @@ def load_library() -> C.CDLL:
                                             C.c_int, DONE_FN, vp]),
         "pa_gradcurv_run_comps2": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.c_int, C.c_int, pi32, C.POINTER(PaCurvParams), C.POINTER(vp), C.POINTER(vp),
                                              C.c_int, C.c_int, DONE2_FN, vp]),
+        "pa_resample_create": (vp, [vp]),
+        "pa_resample_begin": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), C.c_int]),
+        "pa_resample_add_file_level": (C.c_int, [vp, vp, C.c_int, vp, pi32, vp, C.c_int, C.c_int, vp]),
+        "pa_resample_finish": (C.c_int, [vp, vp, C.c_int, C.POINTER(i64)]),
+        "pa_resample_destroy": (None, [vp]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -1108,6 +1113,53 @@ class IntegralAcc:
         out = np.zeros((self.nrows,) + self.shape)
         self.ctx.check(self.ctx.lib.pa_integral_read(self.ctx.h, self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
+
+
+class Resample:
+    """a hierarchy's data on output BoxArrays that are not its own, summed over files (avgPlotfiles.cpp; pa_resample_*).  The caller
+    owns the running multifabs (one per output level) and the work multifabs (every level but the finest, Resample.ghosts)"""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.h = ctx.lib.pa_resample_create(ctx.h)
+        if not self.h:
+            raise PaError(ctx.lib.pa_last_error(ctx.h).decode())
+
+    @staticmethod
+    def ghosts(nlev: int, lev: int, ratios: Sequence[int], interp_type: int = 1) -> int:
+        """ghost layers of the work multifab of level lev (0 on the finest level): ceil(g_finer / ratio) + interp_type"""
+        g = 0
+        for l in range(nlev - 2, lev - 1, -1):
+            g = -(-g // int(ratios[l])) + int(interp_type)
+        return g
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.pa_resample_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def begin(self, running: Sequence["DevMF"], nvar: int):
+        self._keep = list(running)
+        self.ctx.check(self.ctx.lib.pa_resample_begin(self.ctx.h, self.h, len(running), _handles(running), int(nvar)))
+
+    def add_file_level(self, lev: int, file: Optional["DevMF"], comp_map, crse_work: Optional["DevMF"], ratio: int, interp_type: int = 1,
+                       work: Optional["DevMF"] = None):
+        m = np.ascontiguousarray(comp_map, dtype=np.int32)
+        self.ctx.check(self.ctx.lib.pa_resample_add_file_level(self.ctx.h, self.h, int(lev), file.h if file is not None else None,
+                                                               m.ctypes.data_as(C.POINTER(C.c_int32)), crse_work.h if crse_work is not None else None,
+                                                               int(ratio), int(interp_type), work.h if work is not None else None))
+
+    def finish(self, nfiles: int) -> int:
+        """scale by 1.0 / nfiles; returns the number of cells that found no source data"""
+        n = C.c_int64(0)
+        self.ctx.check(self.ctx.lib.pa_resample_finish(self.ctx.h, self.h, int(nfiles), C.byref(n)))
+        return int(n.value)
 
 
 class SurfBin:

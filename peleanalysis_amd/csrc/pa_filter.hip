@@ -8,6 +8,7 @@
 #include "pa_internal.h"
 #include "pa_dist.h"
 #include "pa_fabview.h"
+#include "pa_cclin.h"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -678,41 +679,16 @@ __device__ __forceinline__ void fillpatch2_cell(const DLevelView& L, const DMFVi
       // orc_fillpatch_two_levels): central slopes limited by df/db, one common factor alpha with
       // dumax = sum |s_d| (r-1)/(2r); coarse neighbours beyond a non-periodic wall are the foextrap-filled
       // coarse ghost cells = the nearest cell inside the domain (filterPlt.cpp:164-173)
-      auto cu = [&](int dx, int dy, int dz) -> double {
-        int p[3] = {qc[0] + dx, qc[1] + dy, qc[2] + dz};
+      auto cu = [&](int n) -> double {  // neighbour n = (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1)
+        int p[3] = {qc[0] + n % 3 - 1, qc[1] + (n / 3) % 3 - 1, qc[2] + n / 9 - 1};
         for (int d = 0; d < 3; ++d)
           if (!LC.is_per[d]) { p[d] = max(p[d], LC.domlo[d]); p[d] = min(p[d], LC.domhi[d]); }
         return crse_val(LC, MC, c + cshift, p[0], p[1], p[2], ok);
       };
-      double sl[3];
-      for (int d = 0; d < 3; ++d) {
-        const double um = cu(-(d == 0), -(d == 1), -(d == 2)), up = cu(d == 0, d == 1, d == 2);
-        const double dc = 0.5 * (up - um);
-        const double df = 2.0 * (up - u0), db = 2.0 * (u0 - um);
-        double sx = (df * db >= 0.0) ? fmin(fabs(df), fabs(db)) : 0.0;
-        sx = copysign(1.0, dc) * fmin(sx, fabs(dc));
-        sl[d] = sx;
-      }
-      double alpha = 1.0;
-      if (sl[0] != 0.0 || sl[1] != 0.0 || sl[2] != 0.0) {
-        const double dumax = fabs(sl[0]) * (double)(r - 1) / (double)(2 * r) + fabs(sl[1]) * (double)(r - 1) / (double)(2 * r) +
-                             fabs(sl[2]) * (double)(r - 1) / (double)(2 * r);
-        double umax = u0, umin = u0;
-        for (int dz = -1; dz <= 1; ++dz)
-          for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) {
-              const double v = cu(dx, dy, dz);
-              umin = v < umin ? v : umin;
-              umax = v > umax ? v : umax;
-            }
-        if (dumax * alpha > (umax - u0)) alpha = (umax - u0) / dumax;
-        if (dumax * alpha > (u0 - umin)) alpha = (u0 - umin) / dumax;
-      }
-      double acc = u0;
-      for (int d = 0; d < 3; ++d) {
-        const double xoff = ((double)(q[d] - qc[d] * r) + 0.5) / (double)r - 0.5;
-        acc += xoff * (sl[d] * alpha);
-      }
+      double sl[3], alpha;
+      ccl_slopes<false>(cu, u0, r, sl, alpha);
+      const int rem[3] = {q[0] - qc[0] * r, q[1] - qc[1] * r, q[2] - qc[2] * r};
+      const double acc = ccl_child(u0, sl, alpha, rem, r);
       val = acc;
     }
     if (!ok) atomicAdd(nbad, 1);
@@ -836,41 +812,14 @@ __device__ __forceinline__ void fp_do_item(const DLevelView& L, const DMFView& M
       }
     }
     const double u0 = v[13];
-    double sl[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {  // (unrolled: v[13 +- st] with a run-time st sends the 27 values through scratch memory)
-      const int st = d == 0 ? 1 : (d == 1 ? 3 : 9);
-      const double um = v[13 - st], up = v[13 + st];
-      const double dc = 0.5 * (up - um);
-      const double df = 2.0 * (up - u0), db = 2.0 * (u0 - um);
-      double sx = (df * db >= 0.0) ? fmin(fabs(df), fabs(db)) : 0.0;
-      sx = copysign(1.0, dc) * fmin(sx, fabs(dc));
-      sl[d] = sx;
-    }
-    double alpha = 1.0;
-    if (sl[0] != 0.0 || sl[1] != 0.0 || sl[2] != 0.0) {
-      const double dumax = fabs(sl[0]) * (double)(r - 1) / (double)(2 * r) + fabs(sl[1]) * (double)(r - 1) / (double)(2 * r) +
-                           fabs(sl[2]) * (double)(r - 1) / (double)(2 * r);
-      double umax = u0, umin = u0;
-#pragma unroll
-      for (int n = 0; n < 27; ++n) {  // dz, dy, dx ascending, dx fastest: the order of the per-cell kernel
-        umin = v[n] < umin ? v[n] : umin;
-        umax = v[n] > umax ? v[n] : umax;
-      }
-      if (dumax * alpha > (umax - u0)) alpha = (umax - u0) / dumax;
-      if (dumax * alpha > (u0 - umin)) alpha = (u0 - umin) / dumax;
-    }
+    double sl[3], alpha;
+    ccl_slopes<true>([&](int n) { return v[n]; }, u0, r, sl, alpha);  // (pa_cclin.h: unrolled, so v[] stays in registers)
     if (!ok) atomicAdd(nbad, __popc(mask));
     for (int c8 = 0; c8 < 8; ++c8) {
       if (!((mask >> c8) & 1u)) continue;
       const int q[3] = {r * qc[0] + (c8 & 1), r * qc[1] + ((c8 >> 1) & 1), r * qc[2] + (c8 >> 2)};
-      double acc = u0;
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        const double xoff = ((double)(q[d] - qc[d] * r) + 0.5) / (double)r - 0.5;
-        acc += xoff * (sl[d] * alpha);
-      }
-      f[fab_index(B, M.ng, M.ncomp, c, q[0], q[1], q[2])] = acc;
+      const int rem[3] = {q[0] - qc[0] * r, q[1] - qc[1] * r, q[2] - qc[2] * r};
+      f[fab_index(B, M.ng, M.ncomp, c, q[0], q[1], q[2])] = ccl_child(u0, sl, alpha, rem, r);
     }
   }
 }

@@ -353,6 +353,39 @@ def tagged_hierarchy(base_n: int, nlev: int, fn, bf: int = 16, max_box: int = 12
     return Hierarchy(levels, 2)
 
 
+# ----------------------------------------------------------------------------- unions of overlapping box lists
+def _box_subtract(b, c):
+    """b minus c as a list of disjoint boxes (rows of 6)"""
+    lo, hi = np.maximum(b[:3], c[:3]), np.minimum(b[3:], c[3:])
+    if (lo > hi).any():
+        return [b]
+    out, cur = [], b.copy()
+    for d in range(3):
+        if cur[d] < lo[d]:
+            p = cur.copy()
+            p[3 + d] = lo[d] - 1
+            out.append(p)
+            cur[d] = lo[d]
+        if cur[3 + d] > hi[d]:
+            p = cur.copy()
+            p[d] = hi[d] + 1
+            out.append(p)
+            cur[3 + d] = hi[d]
+    return out
+
+
+def disjoint_cover(boxes, max_size):
+    """disjoint boxes with the union of `boxes` (rows lo0 lo1 lo2 hi0 hi1 hi2, overlaps allowed), chopped to max_size: every box
+    minus the ones before it.  What a union level of avgPlotfiles3d gets (tools/common/pa_avggrids.h holds the tool's own copy)."""
+    done = []
+    for b in np.asarray(boxes, dtype=np.int64).reshape(-1, 6):
+        pieces = [b]
+        for c in done:
+            pieces = [q for p in pieces for q in _box_subtract(p, c)]
+        done.extend(pieces)
+    return np.vstack([chop_box(b[:3], b[3:], max_size) for b in done]).astype(np.int32)
+
+
 # ----------------------------------------------------------------------------- internal re-tiling (pa_level_retile)
 def retile_level(level: Level, max_size=(128, 128, 128), min_thick: int = 3) -> Level:
     """The level on the BoxArray pa_level_retile returns for it: the same cells in fewer, larger boxes (host arithmetic
