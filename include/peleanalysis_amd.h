@@ -301,6 +301,13 @@ int pa_boxfilter_hierarchy(pa_ctx*, int nlev, const pa_mf* const* in, pa_mf* con
 /* the AMREX_SPACEDIM == 2 build of the same call on a level stored as one plane of cells (k = 0):
  * out(i,j,c) = sum_m sum_l (w_l w_m) in(i+l, j+m, c) */
 int pa_boxfilter_level2d(pa_ctx*, const pa_mf* in, pa_mf* out, int scomp, int ncomp, int ng, const double* w);
+/* which kernel the last pa_boxfilter_fab / _level / _level2d call on the context launched, and in what shape (for a hierarchy call: its
+ * last level).  info = {kind, ng, threads per workgroup, rows per y strip TY, y strips, planes per z segment kseg, z segments, refused}:
+ * kind 0 = none yet, 1 = separable, 2 = tap order streaming (box weights), 3 = tap order from an LDS tile, 4 = tap order for any width,
+ * 5 = the 2-D kernel; strips and segments are those of the largest box, the one the launch was shaped for; refused = 1 when the
+ * separable form was asked for and its shape rule declined the boxes, so a tap-order kernel ran instead.  A call that returns before its
+ * launch (bad arguments, a level without boxes) leaves the record as it was.  Returns non-zero for a null argument.  Diagnostic (tests). */
+int pa_filter_last_launch(const pa_ctx*, int32_t info[8]);
 /* filterPlt.cpp:174-203 ghost fill pieces */
 int pa_foextrap(pa_ctx*, pa_mf*, int comp, int ncomp, int ng);
 int pa_fillpatch_two_levels(pa_ctx*, pa_mf* fine, const pa_mf* crse, int comp, int ncomp, int ng, int ratio,

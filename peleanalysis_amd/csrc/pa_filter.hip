@@ -218,7 +218,9 @@ __global__ __launch_bounds__(256) void k_boxfilter_stream(BP bp, int scomp, int 
 // Separable form (the default; PA_FILTER_EXACT=1 keeps the tap-order kernels above).  The filter is a tensor product,
 // out = W_z (W_x (W_y in)), and SURVEY 7.3 / north_star grant 1e-12 relative: three 1-D passes of 2NG+1 taps instead of
 // (2NG+1)^3 taps in the reference's order -- the result differs from the tap-order sum by a few ulp (tested to
-// 1e-12 * Linf against the oracle), and the kernel is bound by HBM (16 B/cell) instead of fp64 issue.
+// 1e-12 * Linf against the oracle; cell by cell within gamma_(4NG+6) * sum |w w w| |q| of the exact sum, and bit for bit equal
+// to the operation order written out below: tests/filter_ref.py sep_bound / sep_model, which must change with it), and the
+// kernel is bound by HBM (16 B/cell) instead of fp64 issue.
 // One z-marching kernel, 512 or 1024 threads: a workgroup owns a strip of TY whole rows of a box (rows of a FAB are contiguous
 // in memory, so a strip + halo is read as one flat, fully coalesced piece; the only re-read is the 2NG halo rows shared
 // with the neighbouring strip, which runs on the same XCD at the same time) and walks kseg + 2NG input planes:
@@ -458,15 +460,31 @@ __global__ __launch_bounds__(256) void k_boxfilter_generic(BP bp, int scomp, int
     }
 }
 
+// what pa_filter_last_launch reports: {kind, ng, threads, TY, y strips, kseg, z segments, refused}, all for the LARGEST box of
+// the launch (the one the launch was shaped for); written on the host, next to the launch it describes
+enum { PA_FK_NONE = 0, PA_FK_SEP = 1, PA_FK_STREAM = 2, PA_FK_TILE = 3, PA_FK_GENERIC = 4, PA_FK_2D = 5 };
+static void filter_note(pa_ctx* ctx, int kind, int ng, int nt, int TY, int nys, int kseg, int nzs, int refused) {
+  const int32_t v[8] = {kind, ng, nt, TY, nys, kseg, nzs, refused};
+  for (int q = 0; q < 8; ++q) ctx->filter_info[q] = v[q];
+}
+static void filter_note_cells(pa_ctx* ctx, int kind, int ng, int nx, int ny, int nz, int refused) {  // the thread-per-cell tiling of tile_grid_dims
+  const int TY = nx <= 32 ? 8 : PA_TY;
+  filter_note(ctx, kind, ng, 256, TY, (ny + TY - 1) / TY, PA_TZ, (nz + PA_TZ - 1) / PA_TZ, refused);
+}
+
 template <typename BP>
-static void filter_launch(hipStream_t st, const BP& bp, int nx, int ny, int nz, unsigned nboxes, int scomp, int ncomp, int ng, const FilterW& W) {
+static void filter_launch(pa_ctx* ctx, const BP& bp, int nx, int ny, int nz, unsigned nboxes, int scomp, int ncomp, int ng, const FilterW& W) {
+  const hipStream_t st = ctx->stream;
   auto grid = [&](int TX, int TY, int TZ) { return dim3(((nx + TX - 1) / TX) * ((ny + TY - 1) / TY) * ((nz + TZ - 1) / TZ), nboxes); };
   // default: the separable form (1e-12 relative); PA_FILTER_EXACT=1: the reference's tap order, bit for bit (read per launch)
   const bool exact = pa_opt().filter_exact != 0;
   SepShape S;
   bool sym = true;  // the separable kernel pairs the taps w_m (a[m] + a[2ng - m]); every filter type of the library is symmetric
   for (int q = 0; q < ng; ++q) sym = sym && W.w[q] == W.w[2 * ng - q];
-  if (!exact && ng >= 1 && sym && sep_shape(nx, ny, nz, ng, nboxes, ncomp, S)) {
+  const bool asked = !exact && ng >= 1 && sym, sep = asked && sep_shape(nx, ny, nz, ng, nboxes, ncomp, S);
+  const int refused = asked && !sep;  // the separable form was asked for and the shape rule said no: the tap-order kernels below
+  if (sep) {
+    filter_note(ctx, PA_FK_SEP, ng, S.nt, S.TY, S.nys, S.kseg, (nz + S.kseg - 1) / S.kseg, 0);
     switch (ng) {
       case 1: sep_dispatch<BP, 1>(st, bp, S, nboxes, scomp, ncomp, W); return;
       case 2: sep_dispatch<BP, 2>(st, bp, S, nboxes, scomp, ncomp, W); return;
@@ -484,11 +502,14 @@ static void filter_launch(hipStream_t st, const BP& bp, int nx, int ny, int nz, 
   if (box && (ng == 1 || ng == 2 || ng == 4)) {
     const int kseg = std::max(1, std::min(32, nz));
     const dim3 g = grid(32, 8, kseg);
+    filter_note(ctx, PA_FK_STREAM, ng, 256, 8, (ny + 7) / 8, kseg, (nz + kseg - 1) / kseg, refused);
     if (ng == 1) hipLaunchKernelGGL((k_boxfilter_stream<BP, 1>), g, dim3(256), 0, st, bp, scomp, ncomp, W.w[1], kseg);
     else if (ng == 2) hipLaunchKernelGGL((k_boxfilter_stream<BP, 2>), g, dim3(256), 0, st, bp, scomp, ncomp, W.w[1], kseg);
     else hipLaunchKernelGGL((k_boxfilter_stream<BP, 4>), g, dim3(256), 0, st, bp, scomp, ncomp, W.w[1], kseg);
     return;
   }
+  if (ng == 1 || ng == 2 || ng == 4) filter_note(ctx, PA_FK_TILE, ng, 256, 8, (ny + 7) / 8, ng == 4 ? 4 : 8, (nz + (ng == 4 ? 4 : 8) - 1) / (ng == 4 ? 4 : 8), refused);
+  else filter_note_cells(ctx, PA_FK_GENERIC, ng, nx, ny, nz, refused);
   if (ng == 1) hipLaunchKernelGGL((k_boxfilter<BP, 1, 32, 8, 8>), grid(32, 8, 8), dim3(256), 0, st, bp, scomp, ncomp, W);
   else if (ng == 2) hipLaunchKernelGGL((k_boxfilter<BP, 2, 32, 8, 8>), grid(32, 8, 8), dim3(256), 0, st, bp, scomp, ncomp, W);
   else if (ng == 4) hipLaunchKernelGGL((k_boxfilter<BP, 4, 32, 8, 4>), grid(32, 8, 4), dim3(256), 0, st, bp, scomp, ncomp, W);
@@ -507,7 +528,7 @@ extern "C" int pa_boxfilter_level(pa_ctx* ctx, const pa_mf* in, pa_mf* out, int 
   if (in->lev->boxes.empty()) return 0;  // a rank that owns no box of this level
   LevelBP2 bp{L->view, in->view, out->view};
   ProfScope prof(ctx, PA_TAG_FILTER);
-  filter_launch(ctx->stream, bp, L->maxn[0], L->maxn[1], L->maxn[2], (unsigned)L->boxes.size(), scomp, ncomp, ng, W);
+  filter_launch(ctx, bp, L->maxn[0], L->maxn[1], L->maxn[2], (unsigned)L->boxes.size(), scomp, ncomp, ng, W);
   PA_HIP(hipGetLastError());
   return 0;
 }
@@ -559,9 +580,16 @@ extern "C" int pa_boxfilter_level2d(pa_ctx* ctx, const pa_mf* in, pa_mf* out, in
   if (in->lev->boxes.empty()) return 0;  // a rank that owns no box of this level
   LevelBP2 bp{L->view, in->view, out->view};
   ProfScope prof(ctx, PA_TAG_FILTER);
+  filter_note_cells(ctx, PA_FK_2D, ng, L->maxn[0], L->maxn[1], L->maxn[2], 0);
   hipLaunchKernelGGL(k_boxfilter2d<LevelBP2>, tile_grid_dims(L->maxn[0], L->maxn[1], L->maxn[2], (unsigned)L->boxes.size()), dim3(256), 0, ctx->stream, bp, scomp,
                      ncomp, ng, W);
   PA_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pa_filter_last_launch(const pa_ctx* ctx, int32_t info[8]) {
+  if (!ctx || !info) return 1;
+  for (int q = 0; q < 8; ++q) info[q] = ctx->filter_info[q];
   return 0;
 }
 
@@ -574,7 +602,7 @@ extern "C" int pa_boxfilter_fab(pa_ctx* ctx, pa_box valid, const pa_fab* in, pa_
   FilterW W;
   for (int q = 0; q < 2 * ng + 1; ++q) W.w[q] = w[q];
   FabBP2 bp{fab_view(*in), fab_view(*out), to_dbox(valid), {1, 1, 1}};
-  filter_launch(ctx->stream, bp, valid.hi[0] - valid.lo[0] + 1, valid.hi[1] - valid.lo[1] + 1, valid.hi[2] - valid.lo[2] + 1, 1, scomp, ncomp, ng, W);
+  filter_launch(ctx, bp, valid.hi[0] - valid.lo[0] + 1, valid.hi[1] - valid.lo[1] + 1, valid.hi[2] - valid.lo[2] + 1, 1, scomp, ncomp, ng, W);
   PA_HIP(hipGetLastError());
   return 0;
 }

@@ -161,6 +161,7 @@ struct pa_ctx {
   int smooth_iters = -1;     // the last do_smooth solve of pa_curvature_run (pa_smooth_last): iterations, relative residual
   double smooth_res = 0.0;
   int curv_path = -1;        // implementation of the last pa_curvature_run (pa_curvature_last_path)
+  int32_t filter_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the last filter launch (pa_filter_last_launch): kind 0 = none yet
   pa_comm comm = {nullptr, 0, 1, nullptr, nullptr};
   struct RcclState* rccl = nullptr;
 };

@@ -79,6 +79,14 @@ def test_box_filter_weights_host_entry(oracle):
                 assert ng == want[0] and np.array_equal(np.array(w[:2 * ng + 1]).view(np.int64), want[1].view(np.int64)), (ftype, fgr)
 
 
+def test_filter_last_launch_host_entry():
+    """pa_filter_last_launch is declared, bound and refuses null arguments without touching the array"""
+    lib = capi.load_library()
+    assert "pa_filter_last_launch" in capi.declared_symbols() and "pa_filter_last_launch" in lib._pa_signatures
+    info = (C.c_int32 * 8)(*range(11, 19))
+    assert lib.pa_filter_last_launch(None, info) != 0 and list(info) == list(range(11, 19))
+
+
 def test_mc_tables_exported_match_oracle(oracle):
     lib = capi.load_library()
     e = np.ctypeslib.as_array(lib.pa_mc_edge_table(), shape=(256,)).astype(np.int32)

@@ -100,8 +100,9 @@ def test_filter_generic_width_and_fab_entry(ctx, oracle, filter_mode):
 @pytest.mark.parametrize("fgr", [12, 16])
 def test_filter_wide_windows(ctx, oracle, filter_mode, fgr):
     """fgr = 12 / 16 (ng = 6 / 8: 13^3 / 17^3 taps, the widths a 3- or 4-level run with base_fgr = 2 .. 6 reaches on its finest
-    level, filterPlt.cpp:132-134): the separable kernel's one-pair-per-thread instantiations (512 and 1024 threads) and the
-    generic tap-order kernel, on a level of mixed box widths (40 and 20 cells: both thread counts) through pa_boxfilter_level"""
+    level, filterPlt.cpp:132-134): the separable kernel's one-pair-per-thread instantiation and the generic tap-order kernel, on a
+    level of mixed box widths (40 and 20 cells) through pa_boxfilter_level.  A level is ONE launch, shaped for its widest box: 512
+    threads and one strip of 20 rows for both widths (the 1024-thread instantiations: tests/test_gpu_filter_shapes.py)"""
     from peleanalysis_amd.hierarchy import Level
     ng = fgr // 2
     boxes = np.vstack([chop_box((0, 0, 0), (39, 19, 19), 40), chop_box((40, 0, 0), (59, 19, 19), 20)])
@@ -119,6 +120,9 @@ def test_filter_wide_windows(ctx, oracle, filter_mode, fgr):
     do = sentinel_out(ctx, dl, 2)
     ctx.check(ctx.lib.pa_boxfilter_level(ctx.h, di.h, do.h, 0, 2, ng, (C.c_double * (2 * ng + 1))(*w)))
     ctx.sync()
+    info = (C.c_int32 * 8)()
+    ctx.check(ctx.lib.pa_filter_last_launch(ctx.h, info))
+    assert tuple(info) == ((1, ng, 512, 20, 1, 20, 1, 0) if filter_mode == "separable" else (4, ng, 256, 4, 5, 16, 2, 0)), tuple(info)
     assert_filter_parity(do.download(), oo, [(0, 0), (1, 1)], f"fgr {fgr}", filter_mode)
 
 
