@@ -17,8 +17,10 @@ def pad_coarse(c, is_per):
     return c
 
 
-def interp_dense(c, r, is_per, interp_type):
-    """the whole fine level (ratio r) interpolated from the dense coarse array c"""
+def interp_dense(c, r, is_per, interp_type, keep=None):
+    """the whole fine level (ratio r) interpolated from the dense coarse array c.  keep: a dict that receives the per-parent
+    intermediates of interp_type 1 (`sl`: the three limited slopes, `alpha`: the common factor), for a caller that has to know
+    which branches of the limiter its data reached"""
     nz, ny, nx = c.shape
     fine = np.empty((nz * r, ny * r, nx * r))
     if interp_type == 0:
@@ -55,6 +57,8 @@ def interp_dense(c, r, is_per, interp_type):
     with np.errstate(divide="ignore", invalid="ignore"):
         alpha = np.where(some & (dumax * alpha > (umax - u0)), (umax - u0) / dumax, alpha)
         alpha = np.where(some & (dumax * alpha > (u0 - umin)), (u0 - umin) / dumax, alpha)
+    if keep is not None:
+        keep.update(sl=sl, alpha=alpha)
     for cz in range(r):
         for cy in range(r):
             for cx in range(r):
