@@ -823,6 +823,39 @@ int pa_resample_add_file_level(pa_ctx*, pa_resample*, int lev, const pa_mf* file
 int pa_resample_finish(pa_ctx*, pa_resample*, int nfiles, int64_t* nosrc);
 void pa_resample_destroy(pa_resample*);
 
+/* ------------------------------------------------- plane sums and slices as images (avgToPlane.cpp / slicePlot.cpp)
+ * One object (pa_plane) reduces a hierarchy to ONE plane normal to `dir` at the resolution of the finest level given to run: width =
+ * length(d0), height = length(d1) with d0 < d1 the two directions other than dir, pixel (i', j') at i' + width * j'.
+ * Composite value F of a cell of that level inside its domain: the value of the finest level <= it whose grids hold the cell's
+ * coarsened image (AmrData::FillVar, piecewise-constant injection; recalled, not restated: DESIGN.md 1).  A cell no level holds is
+ * counted (nosrc) and reads as NaN.  Every level's grids are whole refined cells of the next coarser level's (any AMR plotfile).
+ * Sum (max_grid_size > 0): the sub-box is chopped along dir as BoxArray::maxSize does (even split) into chunks c = 0 .. C-1; per pixel
+ * s_c = (((0.0 + F(a_c)) + F(a_c + 1)) + ... + F(b_c)) over the chunk's cells, ascending, and S = (((0.0 + s_0) + s_1) + ... + s_{C-1}):
+ * plain IEEE additions in that order (a coarse cell R fine cells wide adds its value R times; -0.0 alone gives +0.0); the bits do not
+ * depend on the tiling or the box order of the levels, nor on how the components are grouped.  Slice (max_grid_size == 0): S = F, bits kept.
+ * The hierarchy is walked in place: device memory beyond the levels is the plane (ncomp doubles + 1 byte per pixel) and the chunk table.
+ * One rank; 3-D levels; at most 8 levels.  run is asynchronous on the context's stream; read, minmax and pixelize are synchronous. */
+typedef struct pa_plane pa_plane;
+/* avgToPlane.cpp:93-104, :118-123 (subbox, dir, ba_sub.maxSize) / slicePlot.cpp:51-54 (the domain flattened at sliceloc): ncomp >= 1
+ * rows of the plane; subbox in the finest level's indices; max_grid_size 0 = a slice, subbox one cell thick along dir.  NULL (and
+ * pa_last_error) for dir outside 0..2, an empty sub-box, a slice box thicker than one cell or a plane of more than 2^31 - 1 pixels */
+pa_plane* pa_plane_create(pa_ctx*, int ncomp, int dir, const pa_box* subbox, int max_grid_size);
+/* avgToPlane.cpp:142-202 for every component at once (GetGrids + ParallelCopy, the MFIter loop, ParallelAdd) / slicePlot.cpp:55 (FillVar):
+ * levels[0 .. nlev-1] = level 0 .. finestLevel, ratios[l] = refinement ratio between levels l and l + 1, comps[c] = the component of the
+ * levels' multifabs that becomes row c of the plane.  Fails, launching nothing, for more than 8 levels, a component out of range on any
+ * level, domains that are not each the coarser one refined by the ratio, a sub-box outside the finest domain, sharded levels. */
+int pa_plane_run(pa_ctx*, pa_plane*, int nlev, const pa_mf* const* levels, const int32_t* ratios, const int32_t* comps /* [ncomp] */);
+/* res_mf (avgToPlane.cpp:140, :201) / data (slicePlot.cpp:54): out[ncomp][height][width]; nosrc (may be NULL) = cells of the sub-box no
+ * level holds.  Fails, leaving out alone, without a completed run. */
+int pa_plane_read(pa_ctx*, const pa_plane*, double* out, int64_t* nosrc);
+/* data.min() / data.max() (avgToPlane.cpp:206-207, slicePlot.cpp:56, :61-62) of row comp over the values that are not NaN (FArrayBox's
+ * min / max on a NaN depend on its position); fails when there is none */
+int pa_plane_minmax(pa_ctx*, const pa_plane*, int comp, double* mn, double* mx);
+/* pixelizeData (avgToPlane.cpp:233-270, slicePlot.cpp:95-132) of row comp: t = (v - mn) / (mx - mn); level 0 if !(t > 0) -- a NaN t
+ * included, where the reference's cast is undefined -- else (int)(255 * (t < 1 ? t : 1)).  levels[height][width], host memory. */
+int pa_plane_pixelize(pa_ctx*, const pa_plane*, int comp, double mn, double mx, uint8_t* levels);
+void pa_plane_destroy(pa_plane*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -245,6 +245,12 @@ def load_library() -> C.CDLL:
         "pa_resample_add_file_level": (C.c_int, [vp, vp, C.c_int, vp, pi32, vp, C.c_int, C.c_int, vp]),
         "pa_resample_finish": (C.c_int, [vp, vp, C.c_int, C.POINTER(i64)]),
         "pa_resample_destroy": (None, [vp]),
+        "pa_plane_create": (vp, [vp, C.c_int, C.c_int, C.POINTER(PaBox), C.c_int]),
+        "pa_plane_run": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), pi32, pi32]),
+        "pa_plane_read": (C.c_int, [vp, vp, pdbl, C.POINTER(i64)]),
+        "pa_plane_minmax": (C.c_int, [vp, vp, C.c_int, pdbl, pdbl]),
+        "pa_plane_pixelize": (C.c_int, [vp, vp, C.c_int, dbl, dbl, C.POINTER(C.c_uint8)]),
+        "pa_plane_destroy": (None, [vp]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -1161,6 +1167,61 @@ class Resample:
         n = C.c_int64(0)
         self.ctx.check(self.ctx.lib.pa_resample_finish(self.ctx.h, self.h, int(nfiles), C.byref(n)))
         return int(n.value)
+
+
+class Plane:
+    """a hierarchy reduced to one plane at the finest level's resolution (avgToPlane.cpp / slicePlot.cpp; pa_plane_*): the sums along
+    dir over a sub-box in the reference's order (max_grid_size > 0) or one slice (max_grid_size == 0), min / max, 256 pixel levels"""
+
+    def __init__(self, ctx: Context, ncomp: int, dir: int, subbox, max_grid_size: int):
+        """subbox: (lo0, lo1, lo2, hi0, hi1, hi2) in the finest level's indices"""
+        self.ctx, self.ncomp, self.dir = ctx, int(ncomp), int(dir)
+        bx = PaBox()
+        for d in range(3):
+            bx.lo[d], bx.hi[d] = int(subbox[d]), int(subbox[3 + d])
+        self.h = ctx.lib.pa_plane_create(ctx.h, int(ncomp), int(dir), C.byref(bx), int(max_grid_size))
+        if not self.h:
+            raise PaError(ctx.lib.pa_last_error(ctx.h).decode())
+        d0, d1 = [d for d in range(3) if d != self.dir]
+        self.width, self.height = int(subbox[3 + d0]) - int(subbox[d0]) + 1, int(subbox[3 + d1]) - int(subbox[d1]) + 1
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.pa_plane_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def run(self, levels: Sequence["DevMF"], ratios, comps):
+        """levels: level 0 .. finestLevel; ratios[l]: between levels l and l + 1; comps[c]: the multifab component of row c"""
+        r = np.ascontiguousarray(list(ratios) + [0], dtype=np.int32)
+        m = np.ascontiguousarray(comps, dtype=np.int32)
+        assert len(m) == self.ncomp
+        self.ctx.check(self.ctx.lib.pa_plane_run(self.ctx.h, self.h, len(levels), _handles(levels), r.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 m.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def read(self, out: Optional[np.ndarray] = None):
+        """-> (plane [ncomp][height][width], cells no level holds); out: a C-contiguous float64 array of that shape to fill"""
+        if out is None:
+            out = np.zeros((self.ncomp, self.height, self.width))
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.ncomp, self.height, self.width)
+        n = C.c_int64(0)
+        self.ctx.check(self.ctx.lib.pa_plane_read(self.ctx.h, self.h, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+        return out, int(n.value)
+
+    def minmax(self, comp: int = 0):
+        mn, mx = C.c_double(0.0), C.c_double(0.0)
+        self.ctx.check(self.ctx.lib.pa_plane_minmax(self.ctx.h, self.h, int(comp), C.byref(mn), C.byref(mx)))
+        return mn.value, mx.value
+
+    def pixelize(self, comp: int, mn: float, mx: float) -> np.ndarray:
+        out = np.zeros((self.height, self.width), dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.pa_plane_pixelize(self.ctx.h, self.h, int(comp), float(mn), float(mx), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
 
 
 class SurfBin:
