@@ -1,5 +1,5 @@
 // pa_fixed192.h -- the 192-bit fixed-point arithmetic of the reproducible sums: shared by pa_stats.hip (jpdf,
-// conditionalMean) and pa_integral.hip (integral, rmsVel).  A sum is a two's-complement integer of three 64-bit limbs in units of 2^-s,
+// conditionalMean), pa_integral.hip (integral, rmsVel) and pa_binmef.hip (binMEF).  A sum is a two's-complement integer of three 64-bit limbs in units of 2^-s,
 // s chosen from the declared magnitude M of its terms (scale_of: M < 2^k -> s = 157 - k), added with 64-bit integer atomics and
 // rounded ONCE when it is read (from_fixed).  Integer addition is associative: the order of the adds drops out, bit for bit.
 #pragma once

@@ -19,8 +19,7 @@
 // table is small and the wavefront sum does not already leave one add per tile), which is added to the global one once per workgroup
 // and touched slot; otherwise to the global table.  `uncombined` selects one set of
 // global atomics per cell, with identical bits (tools/integral_bench.py).
-#include "pa_internal.h"
-#include "pa_fixed192.h"
+#include "pa_celltiles.h"
 #include <cmath>
 #include <cstring>
 
@@ -48,18 +47,17 @@ struct pa_integral {
   int s_row[2 * PA_INT_MAXV] = {};
   std::vector<IntLevelTab> tabs;
   int* d_flags = nullptr;
-  int* d_cum = nullptr;
-  size_t cum_cap = 0;
-  std::vector<int> h_cum;
+  CellTileTable tiles;  // of the level being added
 };
 
 struct IntArgs {
   DLevelView L, F;
   DMFView M;
-  const int* cum;
-  int nboxes, ntiles;
+  CellTab T;
   int has_fine, ratio;
-  int kind, dir, dir1, dir2, march, aax, kt, wr, mode;  // mode 0: every cell -> global table; 1: runs -> global table; 2: runs -> LDS table
+  int kind, dir, dir1, dir2;
+  CellWalk W;
+  int wr, mode;  // mode 0: every cell -> global table; 1: runs -> global table; 2: runs -> LDS table
   int lo[3], n2, nslots;
   int nvars, nrows, stride;
   int ccomp;
@@ -69,36 +67,6 @@ struct IntArgs {
   unsigned* flg;
   int* flags;
 };
-
-struct ITile {
-  int b, i, a, m0, m1;
-  DBox B;
-  bool ok;
-};
-// tile t of the level: 256 cells of a plane (x, aax) of one box x kt cells along the march axis
-__device__ __forceinline__ ITile itile_decode(const IntArgs& A, int t) {
-  ITile c;
-  int lo = 0, hi = A.nboxes - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (A.cum[mid] <= t) lo = mid; else hi = mid - 1;
-  }
-  c.b = lo;
-  c.B = A.L.boxes[lo];
-  const unsigned local = (unsigned)(t - A.cum[lo]);
-  const unsigned nx = c.B.hi[0] - c.B.lo[0] + 1, na = c.B.hi[A.aax] - c.B.lo[A.aax] + 1;
-  const unsigned npl = (nx * na + 255u) / 256u;
-  const unsigned mt = local / npl, pt = local - mt * npl;
-  const unsigned p = pt * 256u + threadIdx.x;
-  c.ok = p < nx * na;
-  const unsigned aa = p / nx;
-  c.a = c.B.lo[A.aax] + (int)aa;
-  c.i = c.B.lo[0] + (int)(p - aa * nx);
-  c.m0 = c.B.lo[A.march] + (int)(mt * (unsigned)A.kt);
-  c.m1 = c.m0 + A.kt - 1;
-  if (c.m1 > c.B.hi[A.march]) c.m1 = c.B.hi[A.march];
-  return c;
-}
 
 // one run of a thread (or of a wavefront, or one cell) into a table of the level's layout, in LDS or in HBM
 // the table row (after the measure) of register row r, or -1: the squares sit behind the NV rows of the template in registers and
@@ -178,25 +146,21 @@ __global__ __launch_bounds__(256) void k_integral(IntArgs A) {
   U192 s[NR];
 #pragma unroll
   for (int r = 0; r < NR; ++r) s[r] = {{0, 0, 0}};
-  for (int t = blockIdx.x; t < A.ntiles; t += gridDim.x) {
-    const ITile c = itile_decode(A, t);
+  for (int t = blockIdx.x; t < A.T.ntiles; t += gridDim.x) {
+    const CellTile c = celltile_decode(A.T, A.W, A.L.boxes, t, threadIdx.x);  // a thread without a cell (!c.ok) marches along: the wavefront sums need every lane
     const long long nxg = c.B.hi[0] - c.B.lo[0] + 1 + 2 * A.M.ng, nyg = c.B.hi[1] - c.B.lo[1] + 1 + 2 * A.M.ng,
                     nzg = c.B.hi[2] - c.B.lo[2] + 1 + 2 * A.M.ng;
     const long long cs = pa_cstride(nxg * nyg * nzg, A.M.ncomp);
     int idx[3];
-    idx[0] = c.i;
-    idx[A.aax] = c.a;
-    idx[A.march] = c.m0;
-    const long long ms = A.march == 2 ? nxg * nyg : nxg;
+    celltile_cell(A.W, c, c.m0, idx);
+    const long long ms = A.W.march == 2 ? nxg * nyg : nxg;
     const double* f = A.M.data + A.M.off[c.b] + ((long long)(idx[2] - c.B.lo[2] + A.M.ng) * nyg + (idx[1] - c.B.lo[1] + A.M.ng)) * nxg +
                       (idx[0] - c.B.lo[0] + A.M.ng);
     for (int m = c.m0; m <= c.m1; ++m, f += ms) {  // the bounds are the same for every thread of the workgroup
-      idx[A.march] = m;
+      idx[A.W.march] = m;
+      // integral.cpp:425-436: the cell's refined image has an owner on the next finer level
       bool take = c.ok;
-      if (take && A.has_fine) {  // integral.cpp:425-436: the cell's refined image has an owner on the next finer level
-        const int p[3] = {idx[0] * A.ratio, idx[1] * A.ratio, idx[2] * A.ratio};
-        take = owner_of(A.F, p) == -1;
-      }
+      if (take && A.has_fine) take = !covered_by(A.F, A.ratio, idx[0], idx[1], idx[2]);
       if (take && A.ccomp >= 0) {  // :28, :89, :133 -- a NaN fails both comparisons
         const double vc = f[A.ccomp * cs];
         take = vc >= A.cmin && vc < A.cmax;
@@ -223,23 +187,7 @@ __global__ __launch_bounds__(256) void k_integral(IntArgs A) {
   }
   if (A.wr != PA_WR_NONE) int_wave_flush<NV, NR>(tab, A, key, cnt, s);
   else if (cnt) int_flush<NV, NR>(tab, A, key, cnt, s);
-  if (A.mode == 2) {  // the workgroup's table -> the global one: one add per touched slot and row
-    __syncthreads();
-    const int ne = A.nslots * A.nrows;
-    for (int z = threadIdx.x; z < ne; z += 256) {
-      const int sl = z / A.nrows, r = z - sl * A.nrows;
-      const u64* e = lds + (long long)sl * A.stride;
-      u64* g = A.tab + (long long)sl * A.stride;
-      if (e[0] == 0) continue;  // no cell of this workgroup in the slot
-      if (r == 0) {
-        atomicAdd(g, e[0]);
-      } else {
-        const int o = 1 + 3 * (r - 1);
-        const U192 v = {{e[o], e[o + 1], e[o + 2]}};
-        if (!u192_zero(v)) u192_atomic_add(g + o, v);
-      }
-    }
-  }
+  if (A.mode == 2) celltab_merge(lds, A.tab, A.nslots, A.nrows, A.stride, [](const u64*, u64*) {});  // one add per touched slot and row
   if (flag) atomicOr(A.flags, flag);
 }
 
@@ -262,7 +210,7 @@ extern "C" void pa_integral_destroy(pa_integral* I) {
   if (I->ctx && I->ctx->stream) (void)hipStreamSynchronize(I->ctx->stream);
   integral_free_tabs(I);
   if (I->d_flags) (void)hipFree(I->d_flags);
-  if (I->d_cum) (void)hipFree(I->d_cum);
+  I->tiles.release();
   delete I;
 }
 
@@ -307,8 +255,8 @@ extern "C" int pa_integral_begin(pa_ctx* ctx, pa_integral* I, double w_max, cons
   PaBind bind_(ctx);
   if (!ctx || !I || !vabs) return pa_fail(ctx, "pa_integral_begin: bad argument");
   if (!(w_max > 0.0) || !std::isfinite(w_max)) return pa_fail(ctx, "pa_integral_begin: w_max must be positive and finite");
+  if (check_magnitudes(ctx, "pa_integral_begin", "variable", vabs, I->nvars)) return 1;
   for (int n = 0; n < I->nvars; ++n) {
-    if (!(vabs[n] >= 0.0) || !std::isfinite(vabs[n])) return pa_fail(ctx, "pa_integral_begin: magnitude of variable " + std::to_string(n) + " is not finite");
     I->s_row[n] = scale_of(w_max * vabs[n]);
     if (I->squares) I->s_row[I->nvars + n] = scale_of(w_max * vabs[n] * vabs[n]);
   }
@@ -318,33 +266,6 @@ extern "C" int pa_integral_begin(pa_ctx* ctx, pa_integral* I, double w_max, cons
   integral_free_tabs(I);
   PA_HIP(hipMemsetAsync(I->d_flags, 0, sizeof(int), ctx->stream));
   I->begun = true;
-  return 0;
-}
-
-static int integral_tiles(pa_ctx* ctx, pa_integral* I, const pa_level* lev, int aax, int march, int kt, int& ntiles) {
-  const int nb = (int)lev->boxes.size();
-  I->h_cum.assign(nb + 1, 0);
-  long long tot = 0;
-  for (int b = 0; b < nb; ++b) {
-    const DBox& B = lev->boxes[b];
-    const long long nx = B.hi[0] - B.lo[0] + 1, na = B.hi[aax] - B.lo[aax] + 1, nm = B.hi[march] - B.lo[march] + 1;
-    if (nx * na >= (1LL << 31) - 256) return pa_fail(ctx, "pa_integral: FAB too large");
-    I->h_cum[b] = (int)tot;
-    tot += ((nx * na + 255) / 256) * ((nm + kt - 1) / kt);
-    if (tot >= (1LL << 31)) return pa_fail(ctx, "pa_integral: level too large for one call");
-  }
-  I->h_cum[nb] = (int)tot;
-  if (I->cum_cap < (size_t)nb + 1) {
-    PA_HIP(hipStreamSynchronize(ctx->stream));  // the previous table may still be read by a launch in flight
-    if (I->d_cum) (void)hipFree(I->d_cum);
-    I->d_cum = nullptr;
-    I->cum_cap = 0;
-    PA_HIP(hipMalloc((void**)&I->d_cum, ((size_t)nb + 1) * sizeof(int)));
-    I->cum_cap = (size_t)nb + 1;
-  }
-  PA_HIP(hipMemcpyAsync(I->d_cum, I->h_cum.data(), ((size_t)nb + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-  PA_HIP(hipStreamSynchronize(ctx->stream));  // h_cum is reused by the next call
-  ntiles = (int)tot;
   return 0;
 }
 
@@ -395,19 +316,18 @@ extern "C" int pa_integral_add_level(pa_ctx* ctx, pa_integral* I, const pa_mf* v
   IntArgs A;
   A.L = lev->view;
   A.M = vars->view;
-  A.has_fine = finer ? 1 : 0;
-  A.F = finer ? finer->view : lev->view;
-  A.ratio = ratio;
+  fine_cover(lev, finer, ratio, A.F, A.has_fine, A.ratio);
   A.kind = I->kind; A.dir = I->dir; A.dir1 = I->dir1; A.dir2 = I->dir2;
   // the march direction: one along which the slot does not change, where there is one (x stays the lane direction)
-  A.march = 2; A.aax = 1; A.kt = 16; A.wr = PA_WR_NONE;
+  int march = 2, aax = 1, kt = 16;
+  A.wr = PA_WR_NONE;
   if (I->kind == 3) A.wr = PA_WR_END;
   else if (I->kind == 2) {
-    if (I->dir == 2) { A.march = 1; A.aax = 2; }
-    if (I->dir != 0) A.wr = PA_WR_TILE; else A.kt = 128;  // dir = x: the lane is the slot; long runs, few adds
+    if (I->dir == 2) { march = 1; aax = 2; }
+    if (I->dir != 0) A.wr = PA_WR_TILE; else kt = 128;  // dir = x: the lane is the slot; long runs, few adds
   } else {
-    if (I->dir == 1) { A.march = 1; A.aax = 2; }
-    if (I->dir == 0) A.wr = PA_WR_STEP; else A.kt = 64;
+    if (I->dir == 1) { march = 1; aax = 2; }
+    if (I->dir == 0) A.wr = PA_WR_STEP; else kt = 64;
   }
   // Where the table goes: kind 3 is one slot in LDS.  Kind 2 with dir != x and rows of whole wavefronts (every box a multiple of 64
   // cells wide) leaves one add per wavefront and tile: straight to HBM, no LDS that would cost occupancy.  Otherwise the level's
@@ -428,10 +348,9 @@ extern "C" int pa_integral_add_level(pa_ctx* ctx, pa_integral* I, const pa_mf* v
   A.cmin = cmin; A.cmax = cmax; A.w = w;
   for (int r = 0; r < 2 * PA_INT_MAXV; ++r) A.srow[r] = I->s_row[r];
   A.tab = T->d_tab; A.flg = T->d_flg; A.flags = I->d_flags;
-  if (integral_tiles(ctx, I, lev, A.aax, A.march, A.kt, A.ntiles)) return 1;
-  A.cum = I->d_cum;
-  A.nboxes = (int)lev->boxes.size();
-  const unsigned grid = (unsigned)std::min<long long>(A.ntiles, 1024);
+  A.W = {march, aax, kt};
+  if (I->tiles.build(ctx, lev, aax, march, kt, "pa_integral", A.T)) return 1;
+  const unsigned grid = (unsigned)std::min<long long>(A.T.ntiles, 1024);
   const size_t lb = A.mode == 2 ? lds_bytes : 0;
   const int nv = I->nvars;
   if (I->squares) {
@@ -453,10 +372,7 @@ extern "C" int pa_integral_read(pa_ctx* ctx, const pa_integral* I, double* out) 
   PaBind bind_(ctx);
   if (!ctx || !I || !out) return pa_fail(ctx, "pa_integral_read: bad argument");
   if (!I->begun) return pa_fail(ctx, "pa_integral_read: pa_integral_begin has not been called");
-  int fl = 0;
-  PA_HIP(hipMemcpyAsync(&fl, I->d_flags, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  PA_HIP(hipStreamSynchronize(ctx->stream));
-  if (fl & PA_ST_OVERFLOW) return pa_fail(ctx, "pa_integral_read: a term exceeds the magnitude declared at begin (accumulator overflow)");
+  if (check_sum_flags(ctx, I->d_flags, "pa_integral_read")) return 1;
   const size_t nt = I->tabs.size();
   std::vector<std::vector<u64>> ht(nt);
   std::vector<std::vector<unsigned>> hf(nt);

@@ -17,13 +17,14 @@
 //    so its runs go to a 512-slot cache of hot bins in LDS (claimed by compare-and-swap, never evicted; a run that meets a slot of
 //    another bin goes to the global table) that is added to the global table once per workgroup and used slot.
 //    `uncombined` selects the plain kernel -- one set of global atomics per cell -- with identical bits (tools/stats_bench.py).
-#include "pa_internal.h"
-#include "pa_fixed192.h"
+// The walk itself -- tile table, decode, coverage by the finer level, LDS-table merge -- is pa_celltiles.h's, shared with pa_integral.hip.
+#include "pa_celltiles.h"
 #include <cfloat>
 #include <cmath>
 #include <cstring>
 
 #define PA_STATS_KT 16  // cells a thread marches in z per tile
+typedef CellWalkFixed<1, 2, PA_STATS_KT> StatWalk;  // planes (x, y), march in z
 #define PA_STATS_NP 6   // jpdf: pairs per pass over the cells (4 variables: all of them)
 #define PA_STATS_NA 8   // conditionalMean: averaged components per object
 // doubles as unsigned integers of the same order (per-bin minimum / maximum with integer atomics)
@@ -47,45 +48,6 @@ static double dbl_unsortable(u64 u) {
 __device__ __forceinline__ void wave_count_add(long long* p) {
   const u64 m = __ballot(1);
   if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd((u64*)p, (u64)__popcll(m));
-}
-
-// ---------------------------------------------------------------- tiles: 256 cells of an x-y plane x PA_STATS_KT planes
-struct StatTiles {
-  const int* cum;  // [nboxes + 1] tiles before box b
-  int nboxes, ntiles;
-};
-struct CellIter {
-  int b, i, j, k0, k1;
-  DBox B;
-  bool ok;
-};
-__device__ __forceinline__ CellIter tile_decode(const DLevelView& L, const StatTiles& T, int t) {
-  CellIter c;
-  int lo = 0, hi = T.nboxes - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (T.cum[mid] <= t) lo = mid; else hi = mid - 1;
-  }
-  c.b = lo;
-  c.B = L.boxes[lo];
-  const unsigned local = (unsigned)(t - T.cum[lo]);
-  const unsigned nx = c.B.hi[0] - c.B.lo[0] + 1, ny = c.B.hi[1] - c.B.lo[1] + 1, nz = c.B.hi[2] - c.B.lo[2] + 1;
-  const unsigned npl = (nx * ny + 255u) / 256u;
-  const unsigned kt = local / npl, pt = local - kt * npl;
-  const unsigned p = pt * 256u + threadIdx.x;
-  c.ok = p < nx * ny;
-  const unsigned jj = p / nx;
-  c.j = c.B.lo[1] + (int)jj;
-  c.i = c.B.lo[0] + (int)(p - jj * nx);
-  c.k0 = c.B.lo[2] + (int)(kt * PA_STATS_KT);
-  c.k1 = c.k0 + PA_STATS_KT - 1;
-  if (c.k1 > c.B.hi[2]) c.k1 = c.B.hi[2];
-  (void)nz;
-  return c;
-}
-__device__ __forceinline__ bool covered_by(const DLevelView& F, int ratio, int i, int j, int k) {
-  const int p[3] = {i * ratio, j * ratio, k * ratio};
-  return owner_of(F, p) != -1;
 }
 
 // ================================================================ min / max of several components in one launch
@@ -172,9 +134,7 @@ struct pa_hist {
   size_t acc_words = 0;
   long long* d_cnt = nullptr;  // jpdf: [npairs][5] = v1l v1g v2l v2g nan of the CURRENT add_level call
   int* d_flags = nullptr;
-  int* d_cum = nullptr;        // tile table of the level being added (grow-only)
-  size_t cum_cap = 0;
-  std::vector<int> h_cum;
+  CellTileTable tiles;         // of the level being added
   int s_vol = 0;               // scale exponents
   int s_x[PA_STATS_MAXV] = {};
   int s_sum[PA_STATS_NA] = {}, s_sq[PA_STATS_NA] = {};
@@ -194,36 +154,6 @@ static int hist_reset(pa_ctx* ctx, pa_hist* H) {
   return 0;
 }
 
-static int hist_tiles(pa_ctx* ctx, pa_hist* H, const pa_level* lev, StatTiles& T) {
-  const int nb = (int)lev->boxes.size();
-  H->h_cum.assign(nb + 1, 0);
-  long long tot = 0;
-  for (int b = 0; b < nb; ++b) {
-    const DBox& B = lev->boxes[b];
-    const long long nx = B.hi[0] - B.lo[0] + 1, ny = B.hi[1] - B.lo[1] + 1, nz = B.hi[2] - B.lo[2] + 1;
-    if (nx * ny >= (1LL << 31) - 256) return pa_fail(ctx, "pa_stats: FAB too large");
-    H->h_cum[b] = (int)tot;
-    tot += ((nx * ny + 255) / 256) * ((nz + PA_STATS_KT - 1) / PA_STATS_KT);
-    if (tot >= (1LL << 31)) return pa_fail(ctx, "pa_stats: level too large for one call");
-  }
-  H->h_cum[nb] = (int)tot;
-  if (H->cum_cap < (size_t)nb + 1) {
-    // the previous table may still be read by a launch in flight
-    PA_HIP(hipStreamSynchronize(ctx->stream));
-    if (H->d_cum) (void)hipFree(H->d_cum);
-    H->d_cum = nullptr;
-    H->cum_cap = 0;
-    PA_HIP(hipMalloc((void**)&H->d_cum, ((size_t)nb + 1) * sizeof(int)));
-    H->cum_cap = (size_t)nb + 1;
-  }
-  PA_HIP(hipMemcpyAsync(H->d_cum, H->h_cum.data(), ((size_t)nb + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-  PA_HIP(hipStreamSynchronize(ctx->stream));  // h_cum is reused by the next call
-  T.cum = H->d_cum;
-  T.nboxes = nb;
-  T.ntiles = (int)tot;
-  return 0;
-}
-
 extern "C" void pa_hist_destroy(pa_hist* H) {
   if (!H) return;
   PaBind bind_(H->ctx);
@@ -231,7 +161,7 @@ extern "C" void pa_hist_destroy(pa_hist* H) {
   if (H->d_acc) (void)hipFree(H->d_acc);
   if (H->d_cnt) (void)hipFree(H->d_cnt);
   if (H->d_flags) (void)hipFree(H->d_flags);
-  if (H->d_cum) (void)hipFree(H->d_cum);
+  H->tiles.release();
   delete H;
 }
 
@@ -251,7 +181,7 @@ static pa_hist* hist_alloc(pa_ctx* ctx, pa_hist* H, size_t words, size_t ncnt) {
 struct JpdfArgs {
   DLevelView L, F;
   DMFView M;
-  StatTiles T;
+  CellTab T;
   int has_fine, ratio;
   int nbins, nload, stoich, cond, cvar, normc;
   double cnmin, cnmax, cmin, cmax;
@@ -316,15 +246,15 @@ __global__ __launch_bounds__(256) void k_jpdf(JpdfArgs A) {
     cnt[q] = 0; s1[q] = {{0, 0, 0}}; s2[q] = {{0, 0, 0}};
   };
   for (int t = blockIdx.x; t < A.T.ntiles; t += gridDim.x) {
-    const CellIter c = tile_decode(A.L, A.T, t);
+    const CellTile c = celltile_decode(A.T, StatWalk(), A.L.boxes, t, threadIdx.x);
     if (!c.ok) continue;
     const long long nxg = c.B.hi[0] - c.B.lo[0] + 1 + 2 * A.M.ng, nyg = c.B.hi[1] - c.B.lo[1] + 1 + 2 * A.M.ng,
                     nzg = c.B.hi[2] - c.B.lo[2] + 1 + 2 * A.M.ng;
     const long long cs = pa_cstride(nxg * nyg * nzg, A.M.ncomp);
-    const double* f = A.M.data + A.M.off[c.b] + ((long long)(c.k0 - c.B.lo[2] + A.M.ng) * nyg + (c.j - c.B.lo[1] + A.M.ng)) * nxg +
+    const double* f = A.M.data + A.M.off[c.b] + ((long long)(c.m0 - c.B.lo[2] + A.M.ng) * nyg + (c.a - c.B.lo[1] + A.M.ng)) * nxg +
                       (c.i - c.B.lo[0] + A.M.ng);
-    for (int k = c.k0; k <= c.k1; ++k, f += nxg * nyg) {
-      if (A.has_fine && covered_by(A.F, A.ratio, c.i, c.j, k)) continue;  // jpdf.cpp:373-387, :472
+    for (int k = c.m0; k <= c.m1; ++k, f += nxg * nyg) {
+      if (A.has_fine && covered_by(A.F, A.ratio, c.i, c.a, k)) continue;  // jpdf.cpp:373-387, :472
       double st = 0.0;
       if (A.stoich) {  // jpdf.cpp:410-418
         double sumH = 0.0, sumO = 0.0;
@@ -398,11 +328,9 @@ extern "C" int pa_jpdf_begin(pa_ctx* ctx, pa_hist* H, double vol_max, const doub
   PaBind bind_(ctx);
   if (!ctx || !H || !vabs || H->kind != 1) return pa_fail(ctx, "pa_jpdf_begin: bad argument");
   if (!(vol_max > 0.0) || !std::isfinite(vol_max)) return pa_fail(ctx, "pa_jpdf_begin: vol_max must be positive and finite");
+  if (check_magnitudes(ctx, "pa_jpdf_begin", "variable", vabs, H->nvars)) return 1;
   H->s_vol = scale_of(vol_max);
-  for (int v = 0; v < H->nvars; ++v) {
-    if (!(vabs[v] >= 0.0) || !std::isfinite(vabs[v])) return pa_fail(ctx, "pa_jpdf_begin: magnitude of variable " + std::to_string(v) + " is not finite");
-    H->s_x[v] = scale_of(vol_max * vabs[v]);
-  }
+  for (int v = 0; v < H->nvars; ++v) H->s_x[v] = scale_of(vol_max * vabs[v]);
   if (hist_reset(ctx, H)) return 1;
   H->begun = true;
   return 0;
@@ -426,13 +354,11 @@ extern "C" int pa_jpdf_add_level(pa_ctx* ctx, pa_hist* H, const pa_mf* vars, con
   JpdfArgs A;
   A.L = vars->lev->view;
   A.M = vars->view;
-  A.has_fine = finer ? 1 : 0;
-  A.F = finer ? finer->view : vars->lev->view;
-  A.ratio = ratio;
+  fine_cover(vars->lev, finer, ratio, A.F, A.has_fine, A.ratio);
   if (outside) memset(outside, 0, sizeof(int64_t) * 4 * H->npairs);
   if (nan_cells) memset(nan_cells, 0, sizeof(int64_t) * H->npairs);
   if (vars->lev->boxes.empty()) return 0;
-  if (hist_tiles(ctx, H, vars->lev, A.T)) return 1;
+  if (H->tiles.build(ctx, vars->lev, StatWalk::aax, StatWalk::march, StatWalk::kt, "pa_stats", A.T)) return 1;
   A.nbins = H->nbins; A.nload = nload; A.stoich = P->do_stoichiometry ? 1 : 0;
   A.cond = P->do_conditioning; A.cvar = P->cvar; A.normc = P->norm_cval;
   A.cnmin = P->cnorm_min; A.cnmax = P->cnorm_max; A.cmin = P->cmin; A.cmax = P->cmax;
@@ -467,21 +393,11 @@ extern "C" int pa_jpdf_add_level(pa_ctx* ctx, pa_hist* H, const pa_mf* vars, con
   return 0;
 }
 
-static int hist_check_flags(pa_ctx* ctx, const pa_hist* H, const char* who) {
-  int fl = 0;
-  PA_HIP(hipMemcpyAsync(&fl, H->d_flags, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  PA_HIP(hipStreamSynchronize(ctx->stream));
-  if (fl & PA_ST_BADBIN) return pa_fail(ctx, std::string(who) + ": Bad bin");
-  if (fl & PA_ST_NONFINITE) return pa_fail(ctx, std::string(who) + ": a value that is not finite went into a sum");
-  if (fl & PA_ST_OVERFLOW) return pa_fail(ctx, std::string(who) + ": a term exceeds the magnitude declared at begin (accumulator overflow)");
-  return 0;
-}
-
 extern "C" int pa_jpdf_read(pa_ctx* ctx, const pa_hist* H, double* bin, double* binx1, double* binx2) {
   PaBind bind_(ctx);
   if (!ctx || !H || !bin || !binx1 || !binx2 || H->kind != 1) return pa_fail(ctx, "pa_jpdf_read: bad argument");
   if (!H->begun) return pa_fail(ctx, "pa_jpdf_read: pa_jpdf_begin has not been called");
-  if (hist_check_flags(ctx, H, "pa_jpdf_read")) return 1;
+  if (check_sum_flags(ctx, H->d_flags, "pa_jpdf_read")) return 1;
   std::vector<u64> h(H->acc_words);
   PA_HIP(hipMemcpyAsync(h.data(), H->d_acc, h.size() * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
   PA_HIP(hipStreamSynchronize(ctx->stream));
@@ -502,7 +418,7 @@ extern "C" int pa_jpdf_read(pa_ctx* ctx, const pa_hist* H, double* bin, double* 
 struct CondArgs {
   DLevelView L, F;
   DMFView M;
-  StatTiles T;
+  CellTab T;
   int has_fine, ratio;
   DBox dom;
   int nbins, navg, with_minmax, stride;
@@ -553,17 +469,17 @@ __global__ __launch_bounds__(256) void k_condmean(CondArgs A) {
 #pragma unroll
   for (int a = 0; a < NA; ++a) { sm[a] = {{0, 0, 0}}; sq[a] = {{0, 0, 0}}; mn[a] = ~0ull; mx[a] = 0ull; }
   for (int t = blockIdx.x; t < A.T.ntiles; t += gridDim.x) {
-    const CellIter c = tile_decode(A.L, A.T, t);
+    const CellTile c = celltile_decode(A.T, StatWalk(), A.L.boxes, t, threadIdx.x);
     if (!c.ok) continue;
-    if (c.i < A.dom.lo[0] || c.i > A.dom.hi[0] || c.j < A.dom.lo[1] || c.j > A.dom.hi[1]) continue;  // conditionalMean.cpp:215
+    if (c.i < A.dom.lo[0] || c.i > A.dom.hi[0] || c.a < A.dom.lo[1] || c.a > A.dom.hi[1]) continue;  // conditionalMean.cpp:215
     const long long nxg = c.B.hi[0] - c.B.lo[0] + 1 + 2 * A.M.ng, nyg = c.B.hi[1] - c.B.lo[1] + 1 + 2 * A.M.ng,
                     nzg = c.B.hi[2] - c.B.lo[2] + 1 + 2 * A.M.ng;
     const long long cs = pa_cstride(nxg * nyg * nzg, A.M.ncomp);
-    const double* f = A.M.data + A.M.off[c.b] + ((long long)(c.k0 - c.B.lo[2] + A.M.ng) * nyg + (c.j - c.B.lo[1] + A.M.ng)) * nxg +
+    const double* f = A.M.data + A.M.off[c.b] + ((long long)(c.m0 - c.B.lo[2] + A.M.ng) * nyg + (c.a - c.B.lo[1] + A.M.ng)) * nxg +
                       (c.i - c.B.lo[0] + A.M.ng);
-    for (int k = c.k0; k <= c.k1; ++k, f += nxg * nyg) {
+    for (int k = c.m0; k <= c.m1; ++k, f += nxg * nyg) {
       if (k < A.dom.lo[2] || k > A.dom.hi[2]) continue;
-      if (A.has_fine && covered_by(A.F, A.ratio, c.i, c.j, k)) continue;  // conditionalMean.cpp:246-258, :267
+      if (A.has_fine && covered_by(A.F, A.ratio, c.i, c.a, k)) continue;  // conditionalMean.cpp:246-258, :267
       const double binVal = f[0];
       if (!(binVal >= A.bmin && binVal < A.bmax)) continue;  // :270
       const int myBin = (int)((double)A.nbins * (binVal - A.bmin) / (A.bmax - A.bmin));  // :272
@@ -589,28 +505,14 @@ __global__ __launch_bounds__(256) void k_condmean(CondArgs A) {
     }
   }
   if (MODE != 0 && cnt) cond_flush<NA>(tab, A, key, cnt, sm, sq, mn, mx);
-  if (MODE == 2) {  // the workgroup's table -> the global one: one add per touched entry
-    __syncthreads();
-    const int ne = A.nbins * (1 + 2 * A.navg);  // per bin: hits, navg x (sum, sumsq)
-    for (int z = threadIdx.x; z < ne; z += 256) {
-      const int b = z / (1 + 2 * A.navg), r = z - b * (1 + 2 * A.navg);
-      const u64* e = lds + (long long)b * A.stride;
-      u64* g = A.acc + (long long)b * A.stride;
-      if (e[0] == 0) continue;  // no cell of this workgroup in the bin
-      if (r == 0) {
-        atomicAdd(g, e[0]);
-        if (A.with_minmax)
-          for (int a = 0; a < A.navg; ++a) {
-            atomicMin(g + 1 + 6 * A.navg + a, e[1 + 6 * A.navg + a]);
-            atomicMax(g + 1 + 7 * A.navg + a, e[1 + 7 * A.navg + a]);
-          }
-      } else {
-        const int o = 1 + 3 * (r - 1);
-        const U192 v = {{e[o], e[o + 1], e[o + 2]}};
-        if (!u192_zero(v)) u192_atomic_add(g + o, v);
-      }
-    }
-  }
+  if (MODE == 2)  // the workgroup's table -> the global one: one add per touched entry; per bin: hits, navg x (sum, sumsq), then min / max
+    celltab_merge(lds, A.acc, A.nbins, 1 + 2 * A.navg, A.stride, [&](const u64* e, u64* g) {
+      if (A.with_minmax)
+        for (int a = 0; a < A.navg; ++a) {
+          atomicMin(g + 1 + 6 * A.navg + a, e[1 + 6 * A.navg + a]);
+          atomicMax(g + 1 + 7 * A.navg + a, e[1 + 7 * A.navg + a]);
+        }
+    });
   if (flag) atomicOr(A.flags, flag);
 }
 
@@ -632,8 +534,8 @@ extern "C" int pa_condmean_begin(pa_ctx* ctx, pa_hist* H, int64_t weight_max, co
   PaBind bind_(ctx);
   if (!ctx || !H || !vabs || H->kind != 2) return pa_fail(ctx, "pa_condmean_begin: bad argument");
   if (weight_max < 1) return pa_fail(ctx, "pa_condmean_begin: weight_max must be at least 1");
+  if (check_magnitudes(ctx, "pa_condmean_begin", "component", vabs, H->navg)) return 1;
   for (int a = 0; a < H->navg; ++a) {
-    if (!(vabs[a] >= 0.0) || !std::isfinite(vabs[a])) return pa_fail(ctx, "pa_condmean_begin: magnitude of component " + std::to_string(a) + " is not finite");
     H->s_sum[a] = scale_of((double)weight_max * vabs[a]);
     H->s_sq[a] = scale_of((double)weight_max * vabs[a] * vabs[a]);
   }
@@ -663,11 +565,9 @@ extern "C" int pa_condmean_add_level(pa_ctx* ctx, pa_hist* H, const pa_mf* comps
   CondArgs A;
   A.L = comps->lev->view;
   A.M = comps->view;
-  A.has_fine = finer ? 1 : 0;
-  A.F = finer ? finer->view : comps->lev->view;
-  A.ratio = ratio;
+  fine_cover(comps->lev, finer, ratio, A.F, A.has_fine, A.ratio);
   for (int d = 0; d < 3; ++d) { A.dom.lo[d] = domain->lo[d]; A.dom.hi[d] = domain->hi[d]; }
-  if (hist_tiles(ctx, H, comps->lev, A.T)) return 1;
+  if (H->tiles.build(ctx, comps->lev, StatWalk::aax, StatWalk::march, StatWalk::kt, "pa_stats", A.T)) return 1;
   A.nbins = H->nbins; A.navg = H->navg; A.with_minmax = H->with_minmax; A.stride = H->stride;
   A.bmin = bin_min; A.bmax = bin_max; A.weight = weight;
   for (int a = 0; a < PA_STATS_NA; ++a) { A.ssum[a] = H->s_sum[a]; A.ssq[a] = H->s_sq[a]; }
@@ -687,7 +587,7 @@ extern "C" int pa_condmean_read(pa_ctx* ctx, const pa_hist* H, int64_t* hits, do
   if (!ctx || !H || !hits || !sum || !sumsq || H->kind != 2) return pa_fail(ctx, "pa_condmean_read: bad argument");
   if (!H->begun) return pa_fail(ctx, "pa_condmean_read: pa_condmean_begin has not been called");
   if (H->with_minmax && (!mn || !mx)) return pa_fail(ctx, "pa_condmean_read: the accumulator keeps minima and maxima: mn and mx are needed");
-  if (hist_check_flags(ctx, H, "pa_condmean_read")) return 1;
+  if (check_sum_flags(ctx, H->d_flags, "pa_condmean_read")) return 1;
   std::vector<u64> h(H->acc_words);
   PA_HIP(hipMemcpyAsync(h.data(), H->d_acc, h.size() * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
   PA_HIP(hipStreamSynchronize(ctx->stream));
