@@ -85,7 +85,12 @@ __device__ __forceinline__ double favg(double fl, double fh) { return -(0.5 * (f
 #define PA_TAKE(dst, src) asm volatile("v_mov_b64 %0, %1" : "=v"(dst) : "v"(src))
 #define PA_OPAQUE(x) asm volatile("" : "+v"(x))
 #define PA_LDG(base, off) (*(const double*)((const char*)(base) + (off)))
-#define PA_STG(base, off, v) (*(double*)((char*)(base) + (off)) = (v))
+// PA_STG: a store of an OUTPUT component (the burst of a plane, G of the G-output sweeps, the gradient sweep's four: here,
+// pa_fused_march3n.h, pa_grad_march.h) -- a streaming store (`global_store_dwordx2 ... nt`).  Nothing reads the outputs back
+// within the pass, and as ordinary stores the eight write streams pushed phi out of the XCD's L2 before the neighbouring tile had
+// read the halo rows and columns it shares (round 15: 5.729 -> 5.429 ms per headline pass).  The NCG and compact-array stores, which
+// the fix-up re-reads soon, stay ordinary stores.
+#define PA_STG(base, off, v) __builtin_nontemporal_store((double)(v), (double*)((char*)(base) + (off)))
 
 typedef double pa_d2 __attribute__((ext_vector_type(2)));
 
