@@ -3,7 +3,8 @@ against the dense numpy reference of tests/ghost_ref.py on the matrix of tests/g
 that reference to the oracle and every case to its branch).  Every multifab starts as SENT_GPU in every double but the valid cells
 and is compared WHOLE, bit for bit: the cells a call may write hold the reference's bits, everything else -- layers beyond the ng
 argument, other components, the padding between components, the cells of another call's class, valid cells -- is as it was.  Every
-comparison is of bits or of counts."""
+comparison is of bits or of counts, but one: the coarse-fine face ghosts of pa_apply_bc, which equal the oracle's bits, are ALSO held cell
+by cell to the dense long-double reference of tests/gradcurv_ref.py within its derived bound, so they do not rest on the oracle alone."""
 import ctypes as C
 
 import numpy as np
@@ -11,6 +12,8 @@ import pytest
 
 import ghost_cases as GC
 import ghost_ref as GR
+import gradcurv_cases as GCC
+import gradcurv_ref as GCR
 from peleanalysis_amd import capi
 from util import SENT_GPU, bits_equal, sentinel_count
 
@@ -195,14 +198,18 @@ def test_bad_arguments_are_refused_before_any_launch(ctx):
 def test_apply_bc_matrix(ctx, oracle, options, name, fallbacks):
     """pa_apply_bc on component 2 of 3 with the coarse component 0: the face ghost cells beyond a wall hold +interior / -interior (the
     reference), the coarse-fine ones the oracle's bits (its stencil is held by the polynomial known answers of
-    test_oracle_known_answers.py), and nothing else changed: edge, corner and second-layer ghosts, the other components, the faces of
-    other directions under only_dir.  Without a coarse multifab the coarse-fine face ghosts stay sentinels and pa_bc_errors counts them"""
+    test_oracle_known_answers.py) AND lie within the derived bound of the dense long-double reference of tests/gradcurv_ref.py, which
+    shares no box arithmetic with the oracle or the library; nothing else changed: edge, corner and second-layer ghosts, the other
+    components, the faces of other directions under only_dir.  Without a coarse multifab the coarse-fine face ghosts stay sentinels and
+    pa_bc_errors counts them"""
     case = GC.bc_case(name)
     options(PA_FORCE_FALLBACKS=1 if fallbacks else None)
     init = GC.bc_data(case, SENT_GPU)
     _, BR = GC.bc_ref(name)
+    dense, _ = GCC.bc_ref(name)
     dls = [capi.DevLevel(ctx, lv) for lv in case.levels]
     dmf = [capi.DevMF.from_host(ctx, dl, m) for dl, m in zip(dls, init)]
+    st = GCC.Stat()
     try:
         for l in range(len(case.levels)):
             has_crse = l > 0 and not case.no_coarse
@@ -214,14 +221,26 @@ def test_apply_bc_matrix(ctx, oracle, options, name, fallbacks):
             oracle.lib().orc_apply_bc(oracle._p(oracle._mf(orc)), case.comp, oracle._p(oracle._mf(init[l - 1] if has_crse else None)), case.ccomp, oracle._bc(case.bc),
                                       case.ratio, case.only_dir)
             want = init[l].copy()
-            ncf = 0
+            ncf, masks = 0, []
             for b, B in enumerate(BR[l]):
-                cf, _ = GR.apply_bc(want.fab(b), case.comp, B, case.bc, case.only_dir)
+                cf, wall = GR.apply_bc(want.fab(b), case.comp, B, case.bc, case.only_dir)
                 if has_crse:
                     want.fab(b)[case.comp][cf] = orc.fab(b)[case.comp][cf]
                 ncf += int(cf.sum())
+                masks.append((cf, wall))
             assert ctx.bc_errors() == (0 if has_crse else ncf), f"{name} level {l}"
-            _assert_whole(dmf[l].download(), want, init[l], _stored([init[l]], [want]), f"{name} level {l}")
+            got = dmf[l].download()
+            _assert_whole(got, want, init[l], _stored([init[l]], [want]), f"{name} level {l}")
+            assert dense[l][1] == (0 if has_crse else ncf), f"{name} level {l}: the dense reference counts {dense[l][1]} cells without coarse data"
+            for b, (v, e, cfm, wallm) in enumerate(dense[l][0]):
+                cf, wall = masks[b]
+                assert np.array_equal(GCR.ring1(cf, case.alloc), cfm) and np.array_equal(GCR.ring1(wall, case.alloc), wallm), f"{name} level {l} box {b}: the two references classify alike"
+                if has_crse:
+                    g = GCR.ring1(got.fab(b)[case.comp], case.alloc)
+                    assert sentinel_count(g[cfm], SENT_GPU) == 0 and np.isfinite(g[cfm]).all(), f"{name} level {l} box {b}"
+                    st.add(g[cfm], v[cfm], e[cfm], f"{name} level {l} box {b}: coarse-fine ghost cells against the dense reference")
+        if not case.no_coarse:
+            print(st.check_cap(f"GPU apply_bc {name} (coarse-fine ghosts, dense reference)"))
     finally:
         for d in dmf:
             d.close()
