@@ -4,7 +4,10 @@ the kernels can still go wrong, not the workload's.  Every reference is computed
 
 pa_apply_bc alone: random O(1) data (ghost_cases.random_mf), so a wrong weight shows at O(1).  Pipelines: a tilted ramp in all three
 directions plus a smooth trigonometric term plus noise; no flat region, so |grad c| stays far from the 1e-14 branch of the normal
-(asserted from the reference, ghost cells included: a normal is only ever formed on valid cells, from resolved ghost values)."""
+(asserted from the reference, ghost cells included: a normal is only ever formed on valid cells, from resolved ghost values).
+The options of pa_curvature_run read a velocity at components 1..3 (field_vel, pipe_states(ncomp=4)): ramps and trigonometric terms in
+all three directions in every component plus noise from a generator of its own, so that the scalar and every cached reference of the
+core keep their bits."""
 import dataclasses
 import functools
 
@@ -107,6 +110,28 @@ def _general_levels():
     return H.levels
 
 
+def _tall_levels():
+    """two fine boxes of more than 64 planes in ONE level, a narrow and a wide one.  The options pass (pa_curvopts.hip, k_curvopts) cuts a
+    box into rows of 32 cells (boxes at most 32 wide) or 64, 4 rows per workgroup, and marches z in segments of 64 planes; its grid is
+    sized by the largest box of the level and every box decodes it with its own tile counts.  16 x 10 x 70: rows of 32 with 16 lanes idle,
+    10 = 8 + 2 rows, 70 = 64 + 6 planes.  34 x 6 x 66: one 64-column tile with 30 lanes idle, 6 = 4 + 2 rows, 66 = 64 + 2 planes.  The
+    gap between the two is two coarse cells wide"""
+    per = (1, 0, 0)
+    l0 = Level(np.array([[0, 0, 0, 39, 11, 43]]), (0, 0, 0), (39, 11, 43), per, (0, 0, 0), (1, 1, 1))
+    l1 = Level(np.array([[4, 2, 8, 19, 11, 77], [24, 4, 10, 57, 9, 75]]), (0, 0, 0), (79, 23, 87), per, (0, 0, 0), (1, 1, 1))
+    return [l0, l1]
+
+
+def _kgwide_levels():
+    """every box of every level wider than 32 cells and at least 16 rows tall: pa_curvature_run forms the Gaussian curvature inside the
+    sweep (pa_curvature_last_path == 2) and recomputes the first layer behind special faces.  Fine boxes of 34 x 18 x 10 (34 = 32 + 2
+    columns, 18 = 2 x 8 + 2 rows), staggered in y and z across their shared x face"""
+    per = (1, 0, 0)
+    l0 = Level(np.array([[0, 0, 0, 47, 23, 11]]), (0, 0, 0), (47, 23, 11), per, (0, 0, 0), (1, 1, 1))
+    l1 = Level(np.array([[10, 6, 4, 43, 23, 13], [44, 14, 6, 77, 31, 15]]), (0, 0, 0), (95, 47, 23), per, (0, 0, 0), (1, 1, 1))
+    return [l0, l1]
+
+
 @functools.lru_cache(maxsize=None)
 def pipe_cases():
     C = [
@@ -121,6 +146,10 @@ def pipe_cases():
         PipeCase("general", _general_levels(), (0, 1, 0), "non-convex fine BoxArray: concave corner, partly covered faces (the fused entry points list its irregular cells, pa_fused_irreg.hip; "
                  "pass by pass with fused = 0)", 0.3,
                  ("st3o", "cross_off", "clipped")),
+        PipeCase("tall", _tall_levels(), (0, 0, 0), "a narrow (16 x 10 x 70) and a wide (34 x 6 x 66) fine box in one level: a second z segment of the options pass in both tile "
+                 "shapes, a grid sized by one box and decoded by the other; periodic x, walls y z", 0.3, ("st3c", "cross_on", "nx4", "clipped")),
+        PipeCase("kgwide", _kgwide_levels(), (0, 1, 0), "every box wider than 32 cells and at least 16 rows tall (Gaussian curvature inside the sweep), fine boxes 34 x 18 x 10 "
+                 "staggered across their shared x face; periodic x, reflect-odd y, wall z", 0.3, ("st3c", "cross_on", "nx4", "clipped")),
     ]
     return C
 
@@ -151,18 +180,49 @@ def _pipe_valid(name):
     return out
 
 
-def pipe_states(name, ng, fill_bits=None):
-    """host multifabs (one component, ng ghost layers) with the case's valid data; ghost cells and padding hold fill_bits (NaN if None)"""
+def field_vel(x, y, z):
+    """three velocity components, each a tilted ramp in all three directions plus a trigonometric term in all three: no derivative
+    d u_d / d x_m vanishes, and the divergence (3.3 from the ramps, the trigonometric terms add at most 0.3 * 2 pi + 0.25 * 2 pi +
+    0.2 * 2 pi = 4.7 with changing signs) is of the size of the single derivatives"""
+    tp = 2 * np.pi
+    return (2.0 + 1.3 * x + 0.4 * y - 0.6 * z + 0.3 * np.sin(tp * x + 0.2) * np.cos(tp * y) * np.cos(tp * z + 0.5),
+            -1.0 + 0.5 * x + 0.9 * y + 0.7 * z + 0.25 * np.cos(tp * x) * np.sin(tp * y + 0.3) * np.sin(tp * z),
+            0.5 - 0.8 * x + 0.6 * y + 1.1 * z + 0.2 * np.sin(tp * x + 0.7) * np.sin(tp * y + 0.1) * np.cos(tp * z))
+
+
+@functools.lru_cache(maxsize=None)
+def _pipe_vel_valid(name):
+    """the velocity's valid data, per level per box three arrays; noise of 5 % of a unit slope's step from cell to cell on the level, as
+    the scalar's is, from a generator of its own (the scalar keeps its bits)"""
     case = pipe_case(name)
     out = []
-    for lv, vals in zip(case.levels, _pipe_valid(name)):
-        mf = MultiFab(lv, 1, ng)
+    for l, lv in enumerate(case.levels):
+        rng = np.random.default_rng(1000 * case.seed + l + 500)
+        vals = []
+        for b in range(lv.nboxes):
+            x, y, z = cell_centers(lv, b, 0)
+            vals.append([u + 0.05 * float(lv.dx.min()) * rng.uniform(-1, 1, size=u.shape) for u in field_vel(x, y, z)])
+        out.append(vals)
+    return out
+
+
+def pipe_states(name, ng, fill_bits=None, ncomp=1):
+    """host multifabs (ncomp = 1: one component; ncomp = 4: the velocity at components 1..3; ng ghost layers) with the case's valid data;
+    ghost cells and padding hold fill_bits (NaN if None)"""
+    assert ncomp in (1, 4)
+    case = pipe_case(name)
+    out = []
+    vel = _pipe_vel_valid(name) if ncomp == 4 else None
+    for l, (lv, vals) in enumerate(zip(case.levels, _pipe_valid(name))):
+        mf = MultiFab(lv, ncomp, ng)
         if fill_bits is None:
             mf.data[...] = np.nan
         else:
             mf.data.view(np.uint64)[...] = np.uint64(fill_bits)
         for b in range(lv.nboxes):
             mf.valid(b)[0] = vals[b]
+            for d in range(ncomp - 1):
+                mf.valid(b)[1 + d] = vel[l][b][d]
         out.append(mf)
     return out
 
@@ -183,6 +243,24 @@ def curv_ref(name, threshold, plant=None):
     ref = GCR.Ref(case.levels, 2, plant)
     out = ref.curvature(pipe_states(name, 2), 0, case.bc, threshold)
     return out, ref
+
+
+OPT_NAMES = ("Kg", "SR", "VN") + tuple(f"ROST{q}" for q in range(9))   # output components 5, 6, 7, 8..16
+
+
+def opt_field(o, k):
+    """the F of output component k (5..16) in a level's dict of opts_ref"""
+    return (o["Kg"], o["SR"], o["VN"])[k - 5] if k < 8 else o["ROST"][k - 8]
+
+
+@functools.lru_cache(maxsize=None)
+def opts_ref(name, threshold, plant=None):
+    """(per level dict Kg / SR / VN / ROST, the Ref) of the options on the case's state with the velocity at components 1..3; on top of
+    curv_ref's core (the new plants touch the options alone), which stays as it is"""
+    case = pipe_case(name)
+    core, _ = curv_ref(name, threshold)
+    ref = GCR.Ref(case.levels, 2, plant)
+    return ref.options(pipe_states(name, 2, ncomp=4), 0, 1, case.bc, threshold, core=core), ref
 
 
 # ----------------------------------------------------------------------------- the comparison

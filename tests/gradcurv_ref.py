@@ -1,7 +1,9 @@
 """An independent numpy reference of the grad -> curvature path on DENSE arrays: the coarse-fine half of pa_apply_bc (the wall half is
-ghost_ref.apply_bc's), pa_grad_run and the core of pa_curvature_run / pa_gradcurv_run (Progress, FlameNormal, MeanCurvature, the
-threshold clip).  Restated from the header's contract (include/peleanalysis_amd.h, "ghost cells" and "level-batched kernels"), DESIGN.md
-section 1 and grad.cpp:158-236 / curvature.cpp:137-160, 283-326, 408-570.  No box is ever intersected with another one: per level an
+ghost_ref.apply_bc's), pa_grad_run, the core of pa_curvature_run / pa_gradcurv_run (Progress, FlameNormal, MeanCurvature, the
+threshold clip) and the options of pa_curvature_run (GaussianCurvature, StrainRate, the nine ROST components, VelFlameNormal:
+Ref.options).  Restated from the header's contract (include/peleanalysis_amd.h, "ghost cells", "level-batched kernels", pa_curv_params
+and the comment of pa_curvature_run), DESIGN.md section 1, the quirk list (Q1-Q3, Q12) and grad.cpp:158-236 /
+curvature.cpp:137-160, 283-326, 408-570, 575-789 -- not from pa_curvopts.hip or oracle/.  No box is ever intersected with another one: per level an
 occupancy array over the level's domain (1.0 on valid cells, NaN elsewhere; deep levels on a window, ghost_ref._window) answers "is this
 position covered" by one lookup at the wrapped position, and every field is such a dense array as well.  Imports neither the oracle nor
 the library.  Properly nested hierarchies only: a coarse value that is missing is counted, and the pipelines assert that none is.
@@ -28,22 +30,52 @@ Counted roundings k per stage (refinement ratios 2 and 4 only -- asserted --, so
                                      the input part is |delta g|_2 <= sqrt(sum e_d^2), which holds at every order
   normal n_d = G_d / (-|G|)      1   e = e_d / |G| + |G_d| e_|G| / |G|^2 + gamma_1 |n_d|   (<= 2 e_G / |G| + a few u: |G_d| <= |G|)
   curvature K                    8   a centred difference (6) and the two sums of the three of them (2); the factor 1/2 is exact
+  Hessian H[d][m] = dG_d/dx_m    6   a centred difference of G_d = the cell-centred gradient of c BEFORE its normalisation, unclipped on every
+                                     level (:487-488, :582-613).  Ghost cells of G_d: the level's own values across box faces and periodic
+                                     sides, wall copies / negations with the call's bc (the same for the three components), coarse-fine
+                                     values (17) from the COARSER LEVEL'S G_d; the bound of G enters as dxinv/2 (e_p + e_m)
+  minor a b - c d                2   the two products (1) and their difference (1).  A product a b carries |a| e_b + |b| e_a + gamma_1 |a b|;
+                                     the difference's own rounding is relative to the difference and is counted against |a b| + |c d|, the
+                                     larger: e = gamma_2 (|a b| + |c d|) + |a| e_b + |b| e_a + |c| e_d + |d| e_c
+  quadratic form Q = G^T A G     6   nine products A_ij G_j (1), the sums of three (2), the product with G_i (1), the sum of three (2):
+                                     e = gamma_6 sum |A_ij| |G_i| |G_j| + sum (e_A_ij |G_i| |G_j| + |A_ij| (e_G_i |G_j| + |G_i| e_G_j))
+  Kg = Q / ((gn gn) (gn gn))     4   gn = max(1e-14, |G|) (quirk Q12: pow(x, 4) is (x x)(x x)): three products and the division, and the
+                                     relative bound of |G| four times: e = e_Q / gn^4 + |Kg| (4 e_|G| / |G| + gamma_4).  0 where clipped
+  ROST q = 3 d + m = du_d/dx_m   6   a centred difference of u_d: exact inputs; ghost cells as G's, coarse data the coarser level's velocity
+  StrainRate                     2   (ROST0 + ROST4) + ROST8 -- quirk Q3: the -nn:grad u of :736-744 is overwritten at :745-747 --:
+                                     e = gamma_2 (|R0| + |R4| + |R8|) + e_0 + e_4 + e_8.  Never clipped
+  VelFlameNormal                 3   (u0 n0 + u1 n1) + u2 n2 with the CLIPPED normal: products (1), two sums (2):
+                                     e = gamma_3 sum |u_d n_d| + sum |u_d| e_n_d.  0 where clipped
+G^T A^T G is the same sum as G^T A G: whether the nine lines of :630-638 are read as rows or as columns of the adjugate, or the Hessian's
+two indices exchanged (adj(H^T) = adj(H)^T), cannot be seen in Kg -- next to walls and coarse-fine faces, where H is not symmetric, as
+little as in the interior (test_gradcurv_ref.py::test_transposed_adjugate_is_no_mistake).  What can is the sign each minor carries.
 The progress variable c = (s - pmin) * (1 / (pmax - pmin)) is formed in float64 in exactly that order, so Progress is compared bit for
 bit, c enters the later stages without an error of its own, and the threshold clip (c < thr or c > 1 - thr in float64) is decided on
 the very bits the kernels see.  Clipped cells hold exact zeros.
 
 Measured (worst over the matrix of tests/gradcurv_cases.py; error / (2 e), and 2 e / L-inf of the reference's component per case):
   oracle (CPU tier, test_gradcurv_ref.py)   apply_bc ghosts  err/bound 0.104  bound/Linf 7.1e-15
-                                            grad             err/bound 0.164  bound/Linf 1.5e-12
-                                            FlameNormal      err/bound 0.129  bound/Linf 3.2e-12
-                                            MeanCurvature    err/bound 0.068  bound/Linf 5.8e-11
+                                            grad             err/bound 0.168  bound/Linf 1.5e-12
+                                            FlameNormal      err/bound 0.136  bound/Linf 3.2e-12
+                                            MeanCurvature    err/bound 0.085  bound/Linf 5.8e-11
+                                            (the six cases older than `tall` and `kgwide` alone: 0.164, 0.129, 0.068, as before them)
+                                            GaussianCurvature err/bound 0.062  bound/Linf 3.2e-11
+                                            StrainRate       err/bound 0.167  bound/Linf 3.6e-13
+                                            VelFlameNormal   err/bound 0.097  bound/Linf 2.6e-12
+                                            ROST (9)         err/bound 0.192  bound/Linf 1.7e-12
   kernels (GPU tier, MI355X)                apply_bc ghosts  err/bound 0.104  bound/Linf 9.0e-15  (coarse-fine cells alone)
-                                            grad             err/bound 0.164  bound/Linf 1.5e-12
-                                            FlameNormal      err/bound 0.129  bound/Linf 3.2e-12
-                                            MeanCurvature    err/bound 0.068  bound/Linf 5.8e-11
+                                            grad             err/bound 0.168  bound/Linf 1.5e-12
+                                            FlameNormal      err/bound 0.136  bound/Linf 3.2e-12
+                                            MeanCurvature    err/bound 0.085  bound/Linf 5.8e-11
+                                            GaussianCurvature err/bound 0.062  bound/Linf 3.2e-11  (paths 0, 1 and 2 alike)
+                                            StrainRate       err/bound 0.167  bound/Linf 3.6e-13
+                                            VelFlameNormal   err/bound 0.097  bound/Linf 2.6e-12
+                                            ROST (9)         err/bound 0.192  bound/Linf 1.7e-12
                                             on every entry point and path: the kernels hold the oracle's bits
+(bound / L-inf of every option is largest on `deep`, whose finest level has the smallest cells, but for VelFlameNormal: `wide`.)
 Smallest |planted mistake's shift| / bound over the negative controls of test_gradcurv_ref.py: 7.0e+11 (unclipped coarse normals on case
-`narrow`; that test prints the table with -s)."""
+`narrow`); over those of the options 1.3e+12 (coarse-fine ghost cells of G from the coarser level's normalised normal, on `tall`; that
+test prints the table with -s)."""
 import collections
 import dataclasses
 
@@ -55,8 +87,10 @@ LD = np.longdouble
 U_REF = LD(np.finfo(LD).eps) / 2
 U = LD(2.0) ** -53 + U_REF
 K_GHOST, K_DIFF, K_NORM, K_DIV, K_CURV = 17, 6, 3, 1, 8
+K_MINOR, K_QUAD, K_QUOT, K_SUM3, K_DOT3 = 2, 6, 4, 2, 3
 WHOLE_CELLS = 1 << 19   # a level with at most this many domain cells is held whole (if its coarser level is)
-PLANTS = ("cross_off", "cross_on", "onesided2", "nx4", "bpoint_half", "inside_domain", "odd_sign", "unclipped_coarse_n", "k_not_halved", "plus_max")
+PLANTS = ("cross_off", "cross_on", "onesided2", "nx4", "bpoint_half", "inside_domain", "odd_sign", "unclipped_coarse_n", "k_not_halved", "plus_max",
+          "adj_transposed", "adj_unsigned_minors", "kg_pow3", "coarse_G_normalised", "hessian_of_n", "strain_nn", "rost_transposed", "veln_unclipped_n", "vel_wall_even")
 COUNT_KEYS = ("st1", "st2", "st3c", "st3o", "cross_on", "cross_off", "nx2", "nx3", "nx4", "clipped")
 
 
@@ -242,7 +276,7 @@ class Ref:
             gv, gS, gE = gv + coef[m] * v, gS + abs(coef[m]) * np.abs(v), gE + abs(coef[m]) * e
         return gv, gamma(K_GHOST) * gS + gE, miss
 
-    def apply_bc_box(self, l, b, f: F, fc, bc, only_dir=-1, record=False):
+    def apply_bc_box(self, l, b, f: F, fc, bc, only_dir=-1, record=False, wall_even=False):
         """the box's FAB with one ghost layer after FillBoundary(1) + applyBC: (value, bound) arrays [nz + 2, ny + 2, nx + 2] -- face ghost
         cells resolved (edge and corner ghosts are not part of the operation) --, mask of the coarse-fine face ghost cells, mask of the wall
         ones, number of coarse-fine ghost cells whose coarse data is missing (all of them when fc is None; those are left NaN)"""
@@ -258,7 +292,7 @@ class Ref:
             k = B.cls[g]
             wall, cf = k == 2, k == 1
             assert bc[d] in (1, 2) or not wall.any(), "a periodic direction has no wall"
-            sign = 1 if (bc[d] == 1 or self.plant == "odd_sign") else -1
+            sign = 1 if (bc[d] == 1 or self.plant == "odd_sign" or wall_even) else -1
             nv, ne = np.where(wall, sign * v[i], v[g]), np.where(wall, e[i], e[g])
             wallm[g], cfm[g] = wall, cf
             if cf.any():
@@ -332,6 +366,7 @@ class Ref:
             cv = cs[l].astype(LD)
             fc = F(cv, np.where(np.isnan(cv), LD(np.nan), LD(0)))
             pn = [[] for _ in range(6)]
+            pg = [[] for _ in range(8)]
             for b in range(lv.nboxes):
                 v, e, _, _, nmiss = self.apply_bc_box(l, b, fc, out[l - 1]["cf"] if l else None, bc, record=True)
                 assert nmiss == 0, "not properly nested"
@@ -343,6 +378,11 @@ class Ref:
                 sn = np.sqrt(G[0] * G[0] + G[1] * G[1] + G[2] * G[2])
                 sne = np.sqrt(Ge[0] * Ge[0] + Ge[1] * Ge[1] + Ge[2] * Ge[2]) + gamma(K_NORM) * sn
                 self.min_normgrad = min(self.min_normgrad, float((sn - 2 * sne).min()))
+                for d in range(3):
+                    pg[d].append(G[d])
+                    pg[3 + d].append(Ge[d])
+                pg[6].append(sn)
+                pg[7].append(sne)
                 ng = np.maximum(LD(1e-14), sn)
                 if self.plant != "plus_max":
                     ng = -ng
@@ -375,7 +415,98 @@ class Ref:
                 self.counts["clipped"] += int(clip.sum())
                 Kf = F(np.where(clip, LD(0), Kf.v), np.where(clip, LD(0), Kf.e))
                 nout = [F(np.where(clip, LD(0), f.v), np.where(clip, LD(0), f.e)) for f in nf]
-            out.append(dict(c=cs[l], cf=fc, n=nout, n_unclipped=nf, K=Kf, clip=clip, pmin=pmin, pmax=pmax))
+            Gf = [F(self.paint(l, pg[d]), self.paint(l, pg[3 + d])) for d in range(3)]  # unnormalised and unclipped: what the options differentiate
+            out.append(dict(c=cs[l], cf=fc, n=nout, n_unclipped=nf, K=Kf, clip=clip, pmin=pmin, pmax=pmax, G=Gf, normG=F(self.paint(l, pg[6]), self.paint(l, pg[7]))))
+        return out
+
+    def options(self, states, comp, vel_comp, bc, threshold=None, core=None):
+        """the options of pa_curvature_run (curvature.cpp:575-789) on top of the core (`core`: what self.curvature returned for the same
+        arguments, or None: computed here): per level a dict with "Kg" (F: GaussianCurvature), "SR" (F: StrainRate), "VN" (F: VelFlameNormal)
+        and "ROST" (nine F, q = 3 d + m: d u_d / d x_m)"""
+        if core is None:
+            core = self.curvature(states, comp, bc, threshold)
+        us = [[self.field(l, s, vel_comp + d) for d in range(3)] for l, s in enumerate(states)]
+        out = []
+        for l, lv in enumerate(self.levels):
+            dxi = self.dxinv(l)
+            o = core[l]
+            G, clip = o["G"], o["clip"]
+            # ---- :575-677  H[d][m] = d G_d / d x_m, ghost cells of G_d from the coarser level's G_d, the call's bc for every component
+            src = o["n_unclipped"] if self.plant == "hessian_of_n" else G
+            crse = None
+            if l:
+                crse = core[l - 1]["n" if self.plant in ("coarse_G_normalised", "hessian_of_n") else "G"]
+            pk = [[], []]
+            for b in range(lv.nboxes):
+                H = [[None] * 3 for _ in range(3)]
+                He = [[None] * 3 for _ in range(3)]
+                for d in range(3):
+                    v, e, _, _, nmiss = self.apply_bc_box(l, b, src[d], crse[d] if l else None, bc)
+                    assert nmiss == 0, "not properly nested"
+                    for m in range(3):
+                        hv, S, E = self._cdiff(v, e, m, dxi[m])
+                        H[d][m], He[d][m] = hv, gamma(K_DIFF) * S + E
+                if self.plant == "adj_transposed":
+                    H, He = [[H[m][d] for m in range(3)] for d in range(3)], [[He[m][d] for m in range(3)] for d in range(3)]
+
+                def minor(a, b_, c, d_):
+                    """H[a] H[b] - H[c] H[d] (index pairs): value and bound"""
+                    p, q = H[a[0]][a[1]] * H[b_[0]][b_[1]], H[c[0]][c[1]] * H[d_[0]][d_[1]]
+                    ein = (np.abs(H[a[0]][a[1]]) * He[b_[0]][b_[1]] + np.abs(H[b_[0]][b_[1]]) * He[a[0]][a[1]]
+                           + np.abs(H[c[0]][c[1]]) * He[d_[0]][d_[1]] + np.abs(H[d_[0]][d_[1]]) * He[c[0]][c[1]])
+                    return p - q, gamma(K_MINOR) * (np.abs(p) + np.abs(q)) + ein
+                # A[i][j]: component j of the adjugate's row i, in the index order of :630-638
+                A = [[minor((1, 1), (2, 2), (2, 1), (1, 2)), minor((0, 2), (2, 1), (2, 2), (0, 1)), minor((0, 1), (1, 2), (1, 1), (0, 2))],
+                     [minor((1, 2), (2, 0), (2, 2), (1, 0)), minor((0, 0), (2, 2), (2, 0), (0, 2)), minor((0, 2), (1, 0), (1, 2), (0, 0))],
+                     [minor((1, 0), (2, 1), (2, 0), (1, 1)), minor((0, 1), (2, 0), (2, 1), (0, 0)), minor((0, 0), (1, 1), (1, 0), (0, 1))]]
+                g = [self.valid(l, b, G[d].v) for d in range(3)]
+                ge = [self.valid(l, b, G[d].e) for d in range(3)]
+                Q, QS, QE = LD(0), LD(0), LD(0)
+                for i in range(3):
+                    for j in range(3):
+                        a, ae = A[i][j]
+                        if self.plant == "adj_unsigned_minors" and (i + j) % 2:
+                            a = -a
+                        Q = Q + g[i] * (a * g[j])
+                        QS = QS + np.abs(a) * np.abs(g[i]) * np.abs(g[j])
+                        QE = QE + ae * np.abs(g[i]) * np.abs(g[j]) + np.abs(a) * (ge[i] * np.abs(g[j]) + np.abs(g[i]) * ge[j])
+                sn, sne = self.valid(l, b, o["normG"].v), self.valid(l, b, o["normG"].e)
+                gn = np.maximum(LD(1e-14), sn)
+                den = (gn * gn) * gn if self.plant == "kg_pow3" else (gn * gn) * (gn * gn)
+                kg = Q / den
+                pk[0].append(kg)
+                pk[1].append((gamma(K_QUAD) * QS + QE) / den + np.abs(kg) * (4 * sne / sn + gamma(K_QUOT)))
+            Kg = F(np.where(clip, LD(0), self.paint(l, pk[0])), np.where(clip, LD(0), self.paint(l, pk[1])))
+            # ---- :679-757  ROST q = 3 d + m = d u_d / d x_m, the velocity's ghost cells from the coarser level's velocity, the same bc
+            pr = [[[], []] for _ in range(9)]
+            for b in range(lv.nboxes):
+                for d in range(3):
+                    v, e, _, _, nmiss = self.apply_bc_box(l, b, us[l][d], us[l - 1][d] if l else None, bc, wall_even=self.plant == "vel_wall_even")
+                    assert nmiss == 0, "not properly nested"
+                    for m in range(3):
+                        rv, S, E = self._cdiff(v, e, m, dxi[m])
+                        q = 3 * m + d if self.plant == "rost_transposed" else 3 * d + m
+                        pr[q][0].append(rv)
+                        pr[q][1].append(gamma(K_DIFF) * S + E)
+            R = [F(self.paint(l, pr[q][0]), self.paint(l, pr[q][1])) for q in range(9)]
+            n = o["n"]
+            if self.plant == "strain_nn":  # the first assignment of :736-744, which the second one overwrites (quirk Q3)
+                sr = LD(0)
+                for d in range(3):
+                    for m in range(3):
+                        sr = sr - R[3 * d + m].v * n[d].v * n[m].v
+                SR = F(sr, R[0].e + R[4].e + R[8].e)
+            else:  # not clipped
+                SR = F((R[0].v + R[4].v) + R[8].v, gamma(K_SUM3) * (np.abs(R[0].v) + np.abs(R[4].v) + np.abs(R[8].v)) + (R[0].e + R[4].e + R[8].e))
+            # ---- :761-789  u . n with the clipped normal, (u0 n0 + u1 n1) + u2 n2; an exact zero where clipped
+            if self.plant == "veln_unclipped_n":
+                n = o["n_unclipped"]
+            u = us[l]
+            vn = (u[0].v * n[0].v + u[1].v * n[1].v) + u[2].v * n[2].v
+            vne = gamma(K_DOT3) * (np.abs(u[0].v * n[0].v) + np.abs(u[1].v * n[1].v) + np.abs(u[2].v * n[2].v)) + (np.abs(u[0].v) * n[0].e + np.abs(u[1].v) * n[1].e + np.abs(u[2].v) * n[2].e)
+            if self.plant != "veln_unclipped_n":
+                vn, vne = np.where(clip, LD(0), vn), np.where(clip, LD(0), vne)
+            out.append(dict(Kg=Kg, SR=SR, VN=F(vn, vne), ROST=R))
         return out
 
 

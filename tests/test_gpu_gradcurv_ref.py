@@ -4,7 +4,11 @@ tests/gradcurv_cases.py (the CPU tier, test_gradcurv_ref.py, holds the oracle to
 Outputs start as SENT_GPU everywhere.  Per case, in this order: no coarse data missing (pa_bc_errors); no sentinel and no non-finite
 value in any compared cell, each checked on its own (a NaN fails `<=` only by accident); every compared cell within its bound
 (|got - ref| <= 2 e, gradcurv_ref.py).  No cell is left out: every face ghost cell of pa_apply_bc, every valid cell of every output
-component of the pipelines.  Each test prints its worst error / bound (-s)."""
+component of the pipelines.  Each test prints its worst error / bound (-s).
+The options of pa_curvature_run (GaussianCurvature, StrainRate, VelFlameNormal, the nine ROST components) against Ref.options on all
+three implementations: pass by pass (pa_curvature_last_path 0), one options pass per level (1: k_curvopts, on `tall` with a second
+z segment in both tile shapes and a grid sized by one box and decoded by another) and the Gaussian curvature inside the sweep (2:
+`kgwide`); and the options one by one (the launches of k_curvopts that `every option on` never makes)."""
 import numpy as np
 import pytest
 
@@ -12,7 +16,7 @@ import gradcurv_cases as GCC
 import gradcurv_ref as GCR
 from gradcurv_cases import Stat
 from peleanalysis_amd import capi
-from util import SENT_GPU, SENT_REF, bits_equal, sentinel_count, sentinel_out
+from util import SENT_GPU, SENT_REF, assert_untouched, bits_equal, sentinel_count, sentinel_out
 
 pytestmark = pytest.mark.gpu
 
@@ -82,10 +86,10 @@ def test_apply_bc_matrix(ctx, options, name, fallbacks):
 
 
 # ----------------------------------------------------------------------------- pipelines
-def _dev(ctx, name, ng):
+def _dev(ctx, name, ng, ncomp=1):
     case = GCC.pipe_case(name)
     dls = [capi.DevLevel(ctx, lv) for lv in case.levels]
-    dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, GCC.pipe_states(name, ng, SENT_GPU))]
+    dst = [capi.DevMF.from_host(ctx, dl, s) for dl, s in zip(dls, GCC.pipe_states(name, ng, SENT_GPU, ncomp))]
     return case, dls, dst
 
 
@@ -188,3 +192,107 @@ def test_gradcurv_run(ctx, options, name, key, val, clip):
         _check_curv(case, name, thr, got, None, 7, 4, what)
     finally:
         _close(work + dout + dst + dls)
+
+
+# ----------------------------------------------------------------------------- the options of pa_curvature_run
+def _check_opts(case, name, thr, got, comps, what):
+    """output components `comps` (of 5..16: GaussianCurvature, StrainRate, VelFlameNormal, ROST x 9): written, finite, within the bound;
+    clipped GaussianCurvature and VelFlameNormal exact zeros"""
+    core, ref = GCC.curv_ref(name, thr)
+    out, _ = GCC.opts_ref(name, thr)
+    for k in comps:
+        label = GCC.OPT_NAMES[k - 5]
+        st = Stat()
+        for l, lv in enumerate(case.levels):
+            f = GCC.opt_field(out[l], k)
+            for b in range(lv.nboxes):
+                a = got[l].valid(b)[k]
+                _clean(a, f"{what} {label} level {l} box {b}")
+                st.add(a, ref.valid(l, b, f.v), ref.valid(l, b, f.e), f"{what} {label} level {l} box {b}")
+                if k in (5, 7):
+                    m = ref.valid(l, b, core[l]["clip"])
+                    assert (a[m] == 0.0).all(), f"{what} {label} level {l} box {b}: clipped cells are not zero"
+        print(st.check_cap(f"GPU {what} {label}"))
+
+
+def _state_valid_unchanged(case, name, dst, what):
+    """the call fills ghost cells of the state in place; its valid cells are the uploaded bits"""
+    want = GCC.pipe_states(name, 2, SENT_GPU, 4)
+    for l, lv in enumerate(case.levels):
+        h = dst[l].download()
+        for b in range(lv.nboxes):
+            assert bits_equal(h.valid(b), want[l].valid(b)), f"{what}: valid cells of the state changed, level {l} box {b}"
+
+
+PATH1 = ("narrow", "sym", "ragged", "deep", "wide", "tall")
+
+
+@pytest.mark.parametrize("clip", [False, True], ids=["nothr", "thr"])
+@pytest.mark.parametrize("fused", [False, True], ids=["passes", "fused"])
+@pytest.mark.parametrize("name,key,val", RUNS, ids=RUN_IDS)
+def test_curvature_options_run(ctx, options, name, key, val, fused, clip):
+    """every option on: GaussianCurvature, StrainRate, VelFlameNormal and the nine ROST components within the bound, the five core
+    components within theirs, clipped cells zero, the state's valid cells untouched; the implementation the call took: 2 (Gaussian
+    curvature inside the sweep) on `kgwide`, 1 (one options pass per level) on the cases named in PATH1, 0 pass by pass"""
+    if key:
+        options(**{key: val})
+    case, dls, dst = _dev(ctx, name, 2, 4)
+    thr = case.threshold if clip else None
+    dout = [sentinel_out(ctx, dl, 17) for dl in dls]
+    what = f"pa_curvature_run options {'fused' if fused else 'passes'} {name}{f' {key}={val}' if key else ''} thr {thr}"
+    try:
+        P = capi.curv_params(threshold=thr, fused=fused, do_gauss=True, do_strain=True, strain_tensor=True, do_velnormal=True, vel_comp=1)
+        capi.curvature_run(ctx, dst, 0, case.bc, P, dout, 0)
+        ctx.sync()
+        assert ctx.bc_errors() == 0
+        path = ctx.lib.pa_curvature_last_path(ctx.h)
+        print(f"GPU {what}: path {path}")
+        if not fused:
+            assert path == 0, f"{what}: path {path}"
+        elif key is None and name == "kgwide":
+            assert path == 2, f"{what}: path {path}, not the Gaussian curvature inside the sweep"
+        elif key is None and name in PATH1:
+            assert path == 1, f"{what}: path {path}, not the options pass"
+        got = [d.download() for d in dout]
+        _check_opts(case, name, thr, got, range(5, 17), what)
+        _check_curv(case, name, thr, got, 0, 1, 2, what)
+        _state_valid_unchanged(case, name, dst, what)
+    finally:
+        _close(dout + dst + dls)
+
+
+SUBSETS = {
+    "gauss": (dict(do_gauss=True), [5]),
+    "strain": (dict(do_strain=True), [6]),
+    "strain_tensor": (dict(do_strain=True, strain_tensor=True), [6] + list(range(8, 17))),
+    "veln": (dict(do_velnormal=True), [7]),
+    "strain_veln": (dict(do_strain=True, do_velnormal=True), [6, 7]),
+}
+
+
+@pytest.mark.parametrize("subset", list(SUBSETS))
+@pytest.mark.parametrize("name", ["tall", "wide"])
+def test_curvature_option_subsets(ctx, name, subset):
+    """the options one by one and in pairs, fused, with the threshold: the launches of the options pass that `all options on` never makes
+    (Gaussian curvature alone; strain without the tensor; strain with it and no Gaussian curvature; the normal velocity alone; strain
+    + normal velocity).  The requested components lie within the bound; every component of an option that is off still holds the
+    sentinel"""
+    opts, comps = SUBSETS[subset]
+    case, dls, dst = _dev(ctx, name, 2, 4)
+    thr = case.threshold
+    dout = [sentinel_out(ctx, dl, 17) for dl in dls]
+    what = f"pa_curvature_run {subset} {name} thr {thr}"
+    try:
+        capi.curvature_run(ctx, dst, 0, case.bc, capi.curv_params(threshold=thr, fused=True, vel_comp=1, **opts), dout, 0)
+        ctx.sync()
+        assert ctx.bc_errors() == 0
+        path = ctx.lib.pa_curvature_last_path(ctx.h)
+        assert path == 1, f"{what}: path {path}, not the options pass"
+        got = [d.download() for d in dout]
+        _check_opts(case, name, thr, got, comps, what)
+        _check_curv(case, name, thr, got, 0, 1, 2, what)
+        for l in range(len(case.levels)):
+            assert_untouched(got[l], [k for k in range(5, 17) if k not in comps], f"{what} level {l}")
+        _state_valid_unchanged(case, name, dst, what)
+    finally:
+        _close(dout + dst + dls)

@@ -1,12 +1,14 @@
 """CPU tier of the grad -> curvature reference tests: the dense long-double reference of tests/gradcurv_ref.py against the ORACLE
-(orc_apply_bc, grad_pipeline, curvature_pipeline) on the whole matrix of tests/gradcurv_cases.py, cell by cell within the reference's
+(orc_apply_bc, grad_pipeline, curvature_pipeline with and without its options) on the whole matrix of tests/gradcurv_cases.py, cell by cell within the reference's
 own derived bound; the branches the matrix reaches; the polynomial known answers on the reference itself; and negative controls:
 mistakes planted in the reference that the comparison must see at more than 1000 times the bound.  The GPU tier
 (test_gpu_gradcurv_ref.py) runs the kernels through the same comparison.
 
 Smallest |shift| / bound over the negative controls (the table is printed with -s): 7.0e+11 (unclipped coarse normals on `narrow`; the
 others lie between 1.5e+14 and 1.8e+16.  A cell whose bound is zero -- a wall ghost, a clipped cell -- is rated against one unit
-roundoff of its value)."""
+roundoff of its value).  The controls of the options (GaussianCurvature, StrainRate, ROST, VelFlameNormal): smallest 1.3e+12 (coarse-fine
+ghost cells of G from the coarser level's normalised normal, on `tall`), the others between 4.9e+13 and 9.8e+15.  A transposed adjugate
+is not among them: it is no mistake (test_transposed_adjugate_is_no_mistake); `adj_unsigned_minors` stands where it was meant to."""
 import collections
 
 import numpy as np
@@ -57,6 +59,17 @@ def orc_curv(oracle, name, thr):
         oracle.curvature_pipeline(case.levels, GCC.pipe_states(name, 2), 0, case.bc, oc, 0, MultiFab, threshold=thr)
         _ORC[("curv", name, thr)] = oc
     return _ORC[("curv", name, thr)]
+
+
+def orc_opts(oracle, name, thr):
+    """all 17 components: the core and every option, the velocity at components 1..3"""
+    if ("opts", name, thr) not in _ORC:
+        case = GCC.pipe_case(name)
+        oo = [ref_out(lv, 17) for lv in case.levels]
+        oracle.curvature_pipeline(case.levels, GCC.pipe_states(name, 2, ncomp=4), 0, case.bc, oo, 0, MultiFab, threshold=thr, do_gauss=True, do_strain=True, strain_tensor=True,
+                                  do_velnormal=True, vel_comp=1)
+        _ORC[("opts", name, thr)] = oo
+    return _ORC[("opts", name, thr)]
 
 
 def _thr(case, clip):
@@ -119,6 +132,46 @@ def test_curvature_oracle_within_bound(oracle, name, clip):
                 assert (got[k][m] == 0.0).all(), f"{name} {what} level {l} box {b}: clipped cells are not zero"
                 st.add(got[k], ref.valid(l, b, f(out[l]).v), ref.valid(l, b, f(out[l]).e), f"{name} {what} level {l} box {b}")
         print(st.check_cap(f"curvature {name} thr {thr} {what}"))
+
+
+@pytest.mark.parametrize("clip", [False, True], ids=["nothr", "thr"])
+@pytest.mark.parametrize("name", PIPE)
+def test_options_oracle_within_bound(oracle, name, clip):
+    """GaussianCurvature, StrainRate, VelFlameNormal and the nine ROST components within the bound; clipped GaussianCurvature and
+    VelFlameNormal exactly zero; StrainRate is not clipped (more than nine in ten of the clipped cells hold a reference value that lies
+    beyond twice the comparison's tolerance from zero, and the oracle's is not zero there); the five core components of the same call
+    within theirs"""
+    case = GCC.pipe_case(name)
+    thr = _thr(case, clip)
+    core, ref = GCC.curv_ref(name, thr)
+    out, _ = GCC.opts_ref(name, thr)
+    oo = orc_opts(oracle, name, thr)
+    nclip, nfar = sum(int(o["clip"].sum()) for o in core), 0
+    for k in range(5, 17):
+        st = Stat()
+        for l, lv in enumerate(case.levels):
+            f = GCC.opt_field(out[l], k)
+            for b in range(lv.nboxes):
+                got = oo[l].valid(b)[k]
+                m = ref.valid(l, b, core[l]["clip"])
+                if k in (5, 7):
+                    assert (got[m] == 0.0).all(), f"{name} {GCC.OPT_NAMES[k - 5]} level {l} box {b}: clipped cells are not zero"
+                    assert (ref.valid(l, b, f.v)[m] == 0).all() and (ref.valid(l, b, f.e)[m] == 0).all()
+                if k == 6:  # a clipped cell whose reference value lies beyond its bound from zero: the comparison below tells a zero from it
+                    far = np.abs(ref.valid(l, b, f.v)[m]) > 4 * ref.valid(l, b, f.e)[m]
+                    assert (got[m][far] != 0.0).all(), f"{name} StrainRate level {l} box {b}: clipped"
+                    nfar += int(far.sum())
+                st.add(got, ref.valid(l, b, f.v), ref.valid(l, b, f.e), f"{name} {GCC.OPT_NAMES[k - 5]} level {l} box {b}")
+        print(st.check_cap(f"options {name} thr {thr} {GCC.OPT_NAMES[k - 5]}"))
+    assert nfar > 0.9 * nclip if clip else nclip == 0, f"{name}: {nfar} of {nclip} clipped cells hold a StrainRate that a zero would miss"
+    for what, k, f in (("K", 1, lambda o: o["K"]), ("n0", 2, lambda o: o["n"][0]), ("n1", 3, lambda o: o["n"][1]), ("n2", 4, lambda o: o["n"][2])):
+        st = Stat()
+        for l, lv in enumerate(case.levels):
+            for b in range(lv.nboxes):
+                got = oo[l].valid(b)
+                assert np.array_equal(got[0].view(np.int64), ref.valid(l, b, core[l]["c"]).view(np.int64)), f"{name} Progress level {l} box {b}"
+                st.add(got[k], ref.valid(l, b, f(core[l]).v), ref.valid(l, b, f(core[l]).e), f"{name} {what} with options level {l} box {b}")
+        st.check_cap(f"options {name} thr {thr} {what}")
 
 
 # ----------------------------------------------------------------------------- branches
@@ -222,6 +275,52 @@ def test_reference_cf_cross_term_only_when_all_four_diagonals_are_coarse_fine():
         assert np.abs(err[:2, :] + (16.0 / 35.0) * yy * zz * H * H).max() < 1e-15
 
 
+def test_reference_options_known_answer_quadratic_c_linear_u():
+    """one level without a periodic direction, s a quadratic polynomial, u linear: centred differences are exact for both, so in cells at
+    least two away from every wall G is the analytic gradient, H the analytic (constant) Hessian and grad u the analytic (constant,
+    NOT symmetric) matrix -- ROST q = 3 d + m is told from 3 m + d in every cell --, and Kg is the closed form G^T adj(H) G / |G|^4 of the
+    progress variable c = (s - pmin) / (pmax - pmin).  Tolerance: the inputs are float64 roundings of the polynomials (relative 2^-53 of
+    values below 8); a difference multiplies that by dxinv = 16, the second one again: below 1e-12 on G, 2e-11 on H against entries
+    of the size of 1, and Kg (cubic in them, of the size of 1) is asked to 1e-9"""
+    n = 16
+    L0 = Level(chop_box((0, 0, 0), (n - 1,) * 3, n), (0, 0, 0), (n - 1,) * 3, (0, 0, 0), (0., 0., 0.), (1., 1., 1.))
+    Hs = np.array([[1.4, 0.5, -0.3], [0.5, -0.8, 0.6], [-0.3, 0.6, 1.1]])   # the Hessian of s
+    g0 = np.array([2.0, 1.5, 2.5])                                          # its gradient at the origin: no zero of grad s in the unit cube
+    A = np.array([[0.7, -0.4, 0.3], [0.2, 1.1, -0.5], [-0.6, 0.8, 0.4]])    # d u_d / d x_m
+    u0 = np.array([0.3, -0.2, 0.5])
+
+    def s(x, y, z):
+        X = (x, y, z)
+        return 1.0 + sum(g0[d] * X[d] for d in range(3)) + 0.5 * sum(Hs[d][m] * X[d] * X[m] for d in range(3) for m in range(3))
+    mf = MultiFab(L0, 4, 2)
+    mf.data[...] = np.nan
+    fill_analytic(mf, 0, s)
+    for d in range(3):
+        fill_analytic(mf, 1 + d, lambda x, y, z, d=d: u0[d] + A[d][0] * x + A[d][1] * y + A[d][2] * z)
+    ref = GCR.Ref([L0])
+    core = ref.curvature([mf], 0, (1, 1, 1))
+    out = ref.options([mf], 0, 1, (1, 1, 1), core=core)[0]
+    inv = 1.0 / (core[0]["pmax"] - core[0]["pmin"])
+    x, y, z = cell_centers(L0, 0, 0)
+    X = np.broadcast_arrays(x, y, z, np.zeros((n, n, n)))[:3]
+    G = [inv * (g0[d] + sum(Hs[d][m] * X[m] for m in range(3))) for d in range(3)]
+    H = inv * Hs
+    adj = np.linalg.det(H) * np.linalg.inv(H)     # symmetric: the adjugate's index order does not enter here
+    gn2 = G[0] ** 2 + G[1] ** 2 + G[2] ** 2
+    kg = sum(G[i] * adj[i][j] * G[j] for i in range(3) for j in range(3)) / gn2 ** 2
+    i = (slice(2, -2),) * 3
+    assert np.abs(kg[i]).max() > 0.1
+    assert np.abs(out["Kg"].v[i].astype(np.float64) - kg[i]).max() < 1e-9
+    for d in range(3):
+        for m in range(3):
+            assert np.abs(out["ROST"][3 * d + m].v[i].astype(np.float64) - A[d][m]).max() < 1e-11, (d, m)
+    assert np.abs(out["SR"].v[i].astype(np.float64) - np.trace(A)).max() < 1e-11
+    vn = -sum((u0[d] + sum(A[d][m] * X[m] for m in range(3))) * G[d] for d in range(3)) / np.sqrt(gn2)
+    assert np.abs(out["VN"].v[i].astype(np.float64) - vn[i]).max() < 1e-11
+    for k in range(5, 17):  # and the reference's own bound is finite and small there
+        assert float(GCC.opt_field(out, k).e[i].max()) < 1e-10
+
+
 # ----------------------------------------------------------------------------- negative controls
 def _shift_bc(oracle, name, plant):
     """largest |planted reference - oracle| / bound over the face ghost cells of an applyBC case; a cell whose bound is zero (a wall
@@ -260,11 +359,51 @@ def _shift_curv(oracle, name, plant, clip, comps):
     return worst
 
 
+def _shift_opts(oracle, name, plant, clip):
+    """the same over the twelve option components"""
+    case = GCC.pipe_case(name)
+    thr = _thr(case, clip)
+    bad, ref = GCC.opts_ref(name, thr, plant)
+    good, _ = GCC.opts_ref(name, thr)
+    oo = orc_opts(oracle, name, thr)
+    worst = 0.0
+    for l, lv in enumerate(case.levels):
+        for b in range(lv.nboxes):
+            for k in range(5, 17):
+                got = oo[l].valid(b)[k]
+                v, e = ref.valid(l, b, GCC.opt_field(bad[l], k).v), ref.valid(l, b, GCC.opt_field(good[l], k).e)
+                bd = np.maximum(2 * e, GCR.U * np.maximum(np.abs(got), np.abs(v)))  # (a clipped cell holds 0.0: rated against the planted value)
+                nz = bd > 0
+                if nz.any():
+                    worst = max(worst, float((np.abs(got.astype(LD) - v)[nz] / bd[nz]).max()))
+    return worst
+
+
 CONTROLS = [
     ("cross_off", "bc", "t4_nnn_ng1"), ("cross_on", "bc", "geo_f"), ("onesided2", "bc", "geo_d"), ("nx4", "bc", "t1_nnn_ng2"), ("nx4", "bc", "t2_pnr_ng1"),
     ("bpoint_half", "bc", "t4_nnn_ng1"), ("inside_domain", "bc", "geo_f"), ("odd_sign", "bc", "t1_rpn_ng2"),
     ("unclipped_coarse_n", "curv_thr", "narrow"), ("k_not_halved", "curv", "ragged"), ("plus_max", "curv", "ragged"),
+    # the options.  Interior mixed differences commute, so the two transpositions show only next to walls and coarse-fine faces
+    ("adj_unsigned_minors", "opts", "ragged"), ("adj_unsigned_minors", "opts", "tall"), ("kg_pow3", "opts", "general"), ("coarse_G_normalised", "opts", "tall"),
+    ("hessian_of_n", "opts", "kgwide"), ("strain_nn", "opts", "ragged"), ("rost_transposed", "opts", "sym"), ("rost_transposed", "opts", "kgwide"),
+    ("veln_unclipped_n", "opts_thr", "narrow"), ("vel_wall_even", "opts", "sym"), ("vel_wall_even", "opts", "ragged"),
 ]
+
+
+@pytest.mark.parametrize("name", ["ragged", "tall"])
+def test_transposed_adjugate_is_no_mistake(name):
+    """the plant `adj_transposed` (the nine lines of :630-638 read row by row, or the Hessian's d and m exchanged: adj(H^T) = adj(H)^T) is
+    NOT a negative control: G^T A^T G is the same sum of nine products as G^T A G, whether or not H is symmetric -- next to walls and
+    coarse-fine faces, where the mixed differences do not commute, as well.  The transposed reference equals the plain one to the
+    reference's own rounding in every cell, so no comparison can tell the two readings apart, and none has to.  The index order of the
+    adjugate that does matter -- which minor carries which sign -- is the control `adj_unsigned_minors`"""
+    case = GCC.pipe_case(name)
+    bad, ref = GCC.opts_ref(name, None, "adj_transposed")
+    good, _ = GCC.opts_ref(name, None)
+    for l, lv in enumerate(case.levels):
+        for b in range(lv.nboxes):
+            d = np.abs(ref.valid(l, b, bad[l]["Kg"].v) - ref.valid(l, b, good[l]["Kg"].v))
+            assert (d <= ref.valid(l, b, good[l]["Kg"].e)).all(), f"{name} level {l} box {b}"  # (holds where long double is float64 too)
 
 
 @pytest.mark.parametrize("plant,kind,name", CONTROLS)
@@ -273,6 +412,8 @@ def test_planted_mistake_is_seen(oracle, plant, kind, name):
     named case by more than 1000 times that cell's bound"""
     if kind == "bc":
         r = _shift_bc(oracle, name, plant)
+    elif kind.startswith("opts"):
+        r = _shift_opts(oracle, name, plant, kind == "opts_thr")
     else:
         r = _shift_curv(oracle, name, plant, kind == "curv_thr", [2, 3, 4] if plant == "plus_max" else [1, 2, 3, 4])
     print(f"planted {plant} on {name}: |shift| / bound = {r:.2e}")
