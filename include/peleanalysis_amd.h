@@ -823,6 +823,24 @@ int pa_resample_add_file_level(pa_ctx*, pa_resample*, int lev, const pa_mf* file
 int pa_resample_finish(pa_ctx*, pa_resample*, int nfiles, int64_t* nosrc);
 void pa_resample_destroy(pa_resample*);
 
+/* ------------------------------------------------- one level of one file on a uniform BoxArray, by slabs (flattenAMRFile.cpp)
+ * flattenAMRFile.cpp:77-89 (geom, grid.maxSize, fillPatchFromPlt) for ONE level of ONE file: every valid and ghost cell of
+ * `out` receives V(f, l) as pa_resample defines it; no running sum.  file / comp_map / crse / ratio / interp_type as in
+ * pa_resample_add_file_level; out: nvar (1..16) components on ANY list of disjoint boxes of the level's domain (a slab), any ng.
+ * Asynchronous on the context's stream; *nosrc (device-counted, valid after pa_sync) as in pa_resample_finish.
+ * file may be NULL (no box of the file's level meets the slab), crse is NULL on level 0 only; crse lives on any tiling of the coarser
+ * domain with at least ceil(ng / ratio) + interp_type ghost layers that hold their canonical cells' values.  The file's own cells are
+ * copied as 8 bytes each: a -0.0 and a NaN's payload survive (the running sum's 0.0 + v does not keep them).  Boxes without ghost cells
+ * whose rows start and end on a parent's edge take a kernel that stores whole rows of children as 16-byte vectors, the others the
+ * per-parent code of pa_resample_add_file_level; the bits do not depend on the route, the slab, the order of the boxes or crse's tiling.
+ * (PltFileManager::fillPatchFromPlt is recalled, not restated: semantics stated by this project) */
+int pa_flatten_level(pa_ctx*, const pa_mf* file, const int32_t* comp_map, const pa_mf* crse, int ratio, int interp_type,
+                     pa_mf* out, int nvar, int64_t* nosrc);
+/* what the last call launched, for tests (flattenAMRFile.cpp:89 has no counterpart): boxes on the wide route / on the general route /
+ * skipped as fully covered, overlay rectangles.  The record is ONE per process, not per context (the entry has no context argument):
+ * a hook for single-threaded tests, racy where several contexts or threads flatten at once -- pa_filter_last_launch's lives in its context */
+void pa_flatten_last_launch(int64_t counts[4]);
+
 /* ------------------------------------------------- plane sums and slices as images (avgToPlane.cpp / slicePlot.cpp)
  * One object (pa_plane) reduces a hierarchy to ONE plane normal to `dir` at the resolution of the finest level given to run: width =
  * length(d0), height = length(d1) with d0 < d1 the two directions other than dir, pixel (i', j') at i' + width * j'.

@@ -245,6 +245,8 @@ def load_library() -> C.CDLL:
         "pa_resample_add_file_level": (C.c_int, [vp, vp, C.c_int, vp, pi32, vp, C.c_int, C.c_int, vp]),
         "pa_resample_finish": (C.c_int, [vp, vp, C.c_int, C.POINTER(i64)]),
         "pa_resample_destroy": (None, [vp]),
+        "pa_flatten_level": (C.c_int, [vp, vp, pi32, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(i64)]),
+        "pa_flatten_last_launch": (None, [C.POINTER(i64)]),
         "pa_plane_create": (vp, [vp, C.c_int, C.c_int, C.POINTER(PaBox), C.c_int]),
         "pa_plane_run": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), pi32, pi32]),
         "pa_plane_read": (C.c_int, [vp, vp, pdbl, C.POINTER(i64)]),
@@ -1167,6 +1169,31 @@ class Resample:
         n = C.c_int64(0)
         self.ctx.check(self.ctx.lib.pa_resample_finish(self.ctx.h, self.h, int(nfiles), C.byref(n)))
         return int(n.value)
+
+
+class Flatten:
+    """one level of one file on any list of disjoint boxes of the level's domain, without a running sum (flattenAMRFile.cpp:77-89;
+    pa_flatten_level): the file's own cells bit for bit, the interpolant of the coarser multifab elsewhere"""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self._n = C.c_int64(0)
+
+    ghosts = staticmethod(Resample.ghosts)
+
+    def level(self, file: Optional["DevMF"], comp_map, crse: Optional["DevMF"], ratio: int, interp_type: int, out: "DevMF", nvar: int) -> int:
+        """V(f, l) into every valid and ghost cell of out; waits, and returns the number of cells that found no source data"""
+        m = np.ascontiguousarray(comp_map if comp_map is not None else [0] * int(nvar), dtype=np.int32)
+        self.ctx.check(self.ctx.lib.pa_flatten_level(self.ctx.h, file.h if file is not None else None, m.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     crse.h if crse is not None else None, int(ratio), int(interp_type), out.h, int(nvar), C.byref(self._n)))
+        self.ctx.sync()
+        return int(self._n.value)
+
+    def last_launch(self):
+        """(boxes on the wide route, on the general route, skipped as fully covered, overlay rectangles) of the last call"""
+        a = (C.c_int64 * 4)()
+        self.ctx.lib.pa_flatten_last_launch(a)
+        return tuple(int(x) for x in a)
 
 
 class Plane:

@@ -296,6 +296,7 @@ extern "C" void pa_ctx_destroy(pa_ctx* ctx) {
   if (ctx->d_scr2) (void)hipFree(ctx->d_scr2);
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (ctx->d_mcz) (void)hipFree(ctx->d_mcz);
+  if (ctx->d_flat_nosrc) (void)hipFree(ctx->d_flat_nosrc);
   for (auto& c : ctx->surf_cache) (void)hipFree(c.first);
   for (auto& e : ctx->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   for (auto& e : ctx->sync_evs) (void)hipEventDestroy(e);

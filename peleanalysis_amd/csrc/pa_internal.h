@@ -161,6 +161,7 @@ struct pa_ctx {
   int smooth_iters = -1;     // the last do_smooth solve of pa_curvature_run (pa_smooth_last): iterations, relative residual
   double smooth_res = 0.0;
   int curv_path = -1;        // implementation of the last pa_curvature_run (pa_curvature_last_path)
+  unsigned long long* d_flat_nosrc = nullptr;  // cells without source data of the last pa_flatten_level (pa_flatten.hip), allocated on first use
   int32_t filter_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the last filter launch (pa_filter_last_launch): kind 0 = none yet
   pa_comm comm = {nullptr, 0, 1, nullptr, nullptr};
   struct RcclState* rccl = nullptr;
@@ -270,6 +271,7 @@ struct pa_level {
   mutable std::map<long long, std::unique_ptr<WgTab>> wgtabs;                           // sweep workgroup tables by (group, tile shape) (pa_fused_sweep.hip)
   mutable std::map<long long, std::unique_ptr<struct RsPlan>> rs_plans;                 // restriction onto a sharded coarse level, by coarse level serial (pa_dist.hip)
   mutable std::map<std::pair<long long, int>, std::unique_ptr<struct FpPlan>> fp_plans; // FillPatchTwoLevels parent lists by (coarse level serial, ghost width) (pa_filter.hip)
+  mutable std::map<std::array<long long, 5>, std::unique_ptr<struct FlPlan>> fl_plans;   // launch tables of pa_flatten_level with this level as the output, by (file level serial, ratio, ng, ncomp, alignment) (pa_flatten.hip)
   mutable std::map<std::array<int, 3>, struct pa_mf*> scratch;                          // work multifabs by (components, ghost width, role), kept for the level's lifetime (pa_level_scratch)
   ~pa_level();
 };
@@ -279,6 +281,17 @@ struct FpPlan {
   int n = 0;
   void* d_items = nullptr;  // int4 {box | children mask << 24, parent cell}
   ~FpPlan();
+};
+
+// what pa_flatten_level launches for one (output level, file level) pair (pa_flatten.hip)
+struct FlPlan {
+  int nwide = 0, ngeneral = 0, nskipped = 0, nrect = 0;
+  int nptile = 0, notile = 0, ngtile = 0;  // blocks of k_prolong, of k_overlay, and per general-route box
+  void* d_ptile = nullptr;   // int2 {box, tile of 256 parents}
+  void* d_rects = nullptr;   // FlRect
+  void* d_otile = nullptr;   // int2 {rectangle, tile of 256 cells}
+  int* d_glist = nullptr;    // boxes of the general route
+  ~FlPlan();
 };
 
 struct LevelSpec {

@@ -537,25 +537,19 @@ inline StreamDir read_stream_dir(const std::string& dir) {
   return S;
 }
 
-// WriteMultiLevelPlotfile restated: valid cells of comps [0, names.size()) of each level's HostMF
-inline void write_plotfile(const std::string& path, const std::vector<std::string>& names, const std::vector<Box3>& domains,
-                           const double prob_lo[3], const double prob_hi[3], std::vector<HostMF>& mf, double time,
-                           const std::vector<int>& level_steps, int ref_ratio = 2, int dim = 3, const std::vector<int>* comps = nullptr,
-                           const std::vector<std::vector<Box3>>* file_boxes = nullptr, const std::function<void(int)>* wait_level = nullptr) {
-  // dim = 2: the levels are one plane of cells (k = 0) and the file is what a 2-D AMReX code writes; comps: the HostMF
-  // component behind each name (default: 0, 1, 2, ...); file_boxes: the BoxArray the file gets on each level when the
-  // multifabs live on ANOTHER tiling of the same cells (retile_levels below: the tools compute on merged boxes and write
-  // the input's BoxArray, as grad.cpp:256 does) -- every FAB is then gathered from the multifab boxes it intersects
-  const int nlev = (int)mf.size(), ncomp = (int)names.size();
-  auto wboxes = [&](int l) -> const std::vector<Box3>& { return file_boxes ? (*file_boxes)[l] : mf[l].boxes; };
+// The Header of a plotfile (WriteGenericPlotfileHeader restated): boxes[l] = the BoxArray level l gets in the file.  One copy for
+// write_plotfile and for the streaming writer of flattenAMRFile3d (pa_flatten_plan.h)
+inline void write_plotfile_header(const std::string& path, const std::vector<std::string>& names, const std::vector<Box3>& domains, const double prob_lo[3],
+                                  const double prob_hi[3], const std::vector<const std::vector<Box3>*>& boxes, double time, const std::vector<int>& level_steps,
+                                  int ref_ratio = 2, int dim = 3) {
+  const int nlev = (int)boxes.size(), ncomp = (int)names.size();
+  auto wboxes = [&](int l) -> const std::vector<Box3>& { return *boxes[(size_t)l]; };
   auto bstr = [dim](const Box3& b) {
     if (dim == 3) return box_str(b);
     char s[160];
     std::snprintf(s, sizeof s, "((%d,%d) (%d,%d) (0,0))", b.lo[0], b.lo[1], b.hi[0], b.hi[1]);
     return std::string(s);
   };
-  auto src = [comps](int c) { return comps ? (*comps)[c] : c; };
-  ::mkdir(path.c_str(), 0755);
   {
     std::ofstream f(path + "/Header");
     if (!f) Abort("Unable to create " + path + "/Header");
@@ -586,6 +580,32 @@ inline void write_plotfile(const std::string& path, const std::vector<std::strin
         }
       f << "Level_" << l << "/Cell\n";
     }
+  }
+}
+
+// WriteMultiLevelPlotfile restated: valid cells of comps [0, names.size()) of each level's HostMF
+inline void write_plotfile(const std::string& path, const std::vector<std::string>& names, const std::vector<Box3>& domains,
+                           const double prob_lo[3], const double prob_hi[3], std::vector<HostMF>& mf, double time,
+                           const std::vector<int>& level_steps, int ref_ratio = 2, int dim = 3, const std::vector<int>* comps = nullptr,
+                           const std::vector<std::vector<Box3>>* file_boxes = nullptr, const std::function<void(int)>* wait_level = nullptr) {
+  // dim = 2: the levels are one plane of cells (k = 0) and the file is what a 2-D AMReX code writes; comps: the HostMF
+  // component behind each name (default: 0, 1, 2, ...); file_boxes: the BoxArray the file gets on each level when the
+  // multifabs live on ANOTHER tiling of the same cells (retile_levels below: the tools compute on merged boxes and write
+  // the input's BoxArray, as grad.cpp:256 does) -- every FAB is then gathered from the multifab boxes it intersects
+  const int nlev = (int)mf.size(), ncomp = (int)names.size();
+  auto wboxes = [&](int l) -> const std::vector<Box3>& { return file_boxes ? (*file_boxes)[l] : mf[l].boxes; };
+  auto bstr = [dim](const Box3& b) {
+    if (dim == 3) return box_str(b);
+    char s[160];
+    std::snprintf(s, sizeof s, "((%d,%d) (%d,%d) (0,0))", b.lo[0], b.lo[1], b.hi[0], b.hi[1]);
+    return std::string(s);
+  };
+  auto src = [comps](int c) { return comps ? (*comps)[c] : c; };
+  ::mkdir(path.c_str(), 0755);
+  {
+    std::vector<const std::vector<Box3>*> hb;
+    for (int l = 0; l < nlev; ++l) hb.push_back(&wboxes(l));
+    write_plotfile_header(path, names, domains, prob_lo, prob_hi, hb, time, level_steps, ref_ratio, dim);
   }
   for (int l = 0; l < nlev; ++l) {
     const std::string dir = path + "/Level_" + std::to_string(l);
