@@ -477,6 +477,35 @@ int pa_streamgrad_prepare(pa_ctx*, int nlev, pa_mf* const* state);
 int pa_streamgrad_trace(pa_ctx*, int nlev, pa_mf* const* state, int vcomp, int64_t nnodes, const double* nodes,
                         const int64_t* box_start, const int32_t* ids, int nRKsteps, double hRK, double* strm,
                         int32_t* box_flag);
+/* The alternate surface of stream.cpp (buildAltSurf): build_surface_at_isoVal (:1841-2074), add_thermal_thickness_to_surf
+ * (:1554-1838), add_cold_strain_to_surf (:1369-1552) and add_angle_to_surf (:1211-1367) for every line of the trace, one launch.
+ * A line is column i of a Str box, j = lo .. hi with lo = -nRKh, hi = nRKsteps - 1 - nRKh, nRKh = (nRKsteps - 1) / 2.
+ * locate(c, val) -> (lIdx, rIdx, frac): (lo, lo + 1, 0) when val <= v(lo) or a comparison meets a NaN [branch 0]; (hi - 1, hi, 1)
+ * when val > v(hi) [3]; else the first j with val >= v(j) && val < v(j + 1) and frac = (val - v(j)) / (v(j + 1) - v(j)), 0 when
+ * the two are equal [1]; (hi, hi, 0) when no segment qualifies [2].  lerp(c) = xL + (xR - xL) * frac; arc = the signed distance
+ * along the line from j = 0, summed in increasing j with the located segment weighted by frac (or 1 - frac below j = 0).
+ * strm, box_start, ids: as pa_streamgrad_trace takes and writes them (strm and ids on the device, box_start on the host, nbox
+ * boxes of all levels), ncs components per point.  out: device [nout][nNodes], node id - 1 of the line decides the column:
+ *   X Y Z and the ncarry components `carry` = lerp at locate(isoComp, altVal); then arc there;
+ *   thickComp >= 0: arc(locate(thickComp, thickHi)) - arc(locate(thickComp, thickLo));
+ *   TComp >= 0: lerp(strainComp) at locate(TComp, TVal);
+ *   addAngle: dx[2] / |dx| with dx = x(h - 1) - x(h + 1), h = (int)(0.5 * (lo + hi)) -- the COSINE: the caller applies acos.
+ * branch: device int8 [nquery][nNodes] or NULL: the branch 0 .. 3 above of the queries alt, thickLo, thickHi, T (those asked for,
+ * in this order).  Every operation is an IEEE add, multiply, divide or sqrt in the reference's association: the serial code's bits.
+ * Fails (pa_last_error) on a component outside 0 .. ncs - 1, nRKsteps < 3, more than 8 carried components, a box_start that
+ * does not ascend from 0, and a node id outside 1 .. nNodes (checked on the device before anything is written).  Synchronous. */
+typedef struct {
+  int32_t isoComp;            /* the progress variable among the line's components */
+  double  altVal;
+  int32_t ncarry, carry[8];
+  int32_t thickComp;          /* < 0: no thickness */
+  double  thickLo, thickHi;
+  int32_t TComp, strainComp;  /* TComp < 0: no cold strain */
+  double  TVal;
+  int32_t addAngle;
+} pa_streamalt_params;
+int pa_streamalt_run(pa_ctx*, int32_t nbox, const int64_t* box_start, const int32_t* ids, const double* strm, int32_t ncs,
+                     int32_t nRKsteps, int64_t nNodes, const pa_streamalt_params* p, double* out, int8_t* branch);
 
 /* ------------------------------------------------------------- sampling along streamlines (sampleStreamlines.cpp / _nd.f90)
  * The arithmetic is sampleStreamlines_nd.f90's: ntrpv WITHOUT the [plo, phi] test (b = FLOOR((x-plo)/dx - 0.5), n clamped

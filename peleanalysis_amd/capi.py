@@ -35,6 +35,12 @@ class PaCurvParams(C.Structure):
                 ("spacedim", C.c_int32)]
 
 
+class PaStreamAltParams(C.Structure):
+    _fields_ = [("isoComp", C.c_int32), ("altVal", C.c_double), ("ncarry", C.c_int32), ("carry", C.c_int32 * 8), ("thickComp", C.c_int32),
+                ("thickLo", C.c_double), ("thickHi", C.c_double), ("TComp", C.c_int32), ("strainComp", C.c_int32), ("TVal", C.c_double),
+                ("addAngle", C.c_int32)]
+
+
 class PaXfer(C.Structure):
     _fields_ = [("peer", C.c_int32), ("sendbuf", C.c_void_p), ("nsend", C.c_int64), ("recvbuf", C.c_void_p), ("nrecv", C.c_int64)]
 
@@ -187,6 +193,7 @@ def load_library() -> C.CDLL:
                                     pi32]),
         "pa_streamgrad_prepare": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
         "pa_streamgrad_trace": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.c_int, i64, vp, C.POINTER(i64), vp, C.c_int, dbl, vp, pi32]),
+        "pa_streamalt_run": (C.c_int, [vp, i32, C.POINTER(i64), vp, vp, i32, i32, i64, C.POINTER(PaStreamAltParams), vp, vp]),
         "pa_interpstream_fab": (C.c_int, [vp, C.POINTER(PaFab), i32, C.POINTER(PaFab), i32, C.POINTER(PaFab), pdbl, pdbl, pi32]),
         "pa_set_distance_fab": (C.c_int, [vp, C.POINTER(PaFab), C.POINTER(PaFab)]),
         "pa_streamsample_run": (C.c_int, [vp, C.c_int, C.POINTER(vp), i32, pdbl, pdbl, pi32, pi32, pi32, pi32, pi32, vp, vp, i32, i32, i32, pi32]),
@@ -745,6 +752,49 @@ def streamgrad_trace(ctx: Context, states: Sequence[DevMF], nodes: np.ndarray, i
         out.append(o)
         fl.append(f)
     return out, fl
+
+
+def streamalt_nout(carry=(), thickComp=-1, TComp=-1, addAngle=False):
+    """components and queries of pa_streamalt_run for these options -> (nout, nquery)"""
+    return 3 + len(carry) + 1 + (thickComp >= 0) + (TComp >= 0) + bool(addAngle), 1 + 2 * (thickComp >= 0) + (TComp >= 0)
+
+
+def streamalt_run(ctx: Context, lines, ins, nRKsteps: int, nNodes: int, isoComp: int, altVal: float, carry=(), thickComp: int = -1, thickLo: float = 0.0,
+                  thickHi: float = 0.0, TComp: int = -1, TVal: float = 0.0, strainComp: int = -1, addAngle: bool = False, with_branch: bool = True,
+                  out_fill=None, ncs: Optional[int] = None):
+    """pa_streamalt_run on lines in streamgrad_trace's form: lines[l][b] = [ncs][nRKsteps][n] or None, ins[l][b] = the 1-based node ids
+    of those lines; or lines = (DevBuf of the trace's flat buffer, ncs).  out_fill: the uint64 bit pattern every output double
+    starts with (the int8 branch codes start as -1).  -> (out [nout][nNodes] -- the angle column holds the COSINE --, branch int8
+    [nquery][nNodes] or None)"""
+    counts = [len(ids) for per in ins for ids in per]
+    start = np.zeros(len(counts) + 1, dtype=np.int64)
+    start[1:] = np.cumsum(counts)
+    nlines = int(start[-1])
+    allids = np.concatenate([np.asarray(ids, np.int32) for per in ins for ids in per] + [np.zeros(0, np.int32)])
+    if isinstance(lines, tuple):
+        sb, ncs = lines
+    else:
+        live = [np.ascontiguousarray(x, dtype=np.float64) for per in lines for x in per if x is not None]
+        if ncs is None:
+            ncs = live[0].shape[0]
+        sb = _dev(ctx, np.concatenate([x.ravel() for x in live] + [np.zeros(0)]))
+    ib = _dev(ctx, allids)
+    nout, nq = streamalt_nout(carry, thickComp, TComp, addAngle)
+    fill = np.full(nout * max(nNodes, 1), np.nan) if out_fill is None else np.full(nout * max(nNodes, 1), out_fill, dtype=np.uint64).view(np.float64)
+    ob = DevBuf.from_numpy(ctx, fill)
+    bb = DevBuf.from_numpy(ctx, np.full(max(nq * nNodes, 8), -1, dtype=np.int8)) if with_branch else None
+    P = PaStreamAltParams()
+    P.isoComp, P.altVal, P.ncarry = int(isoComp), float(altVal), len(carry)
+    if len(carry) > 8:
+        raise PaError("pa_streamalt_run: more than 8 carried components")
+    for k, c in enumerate(carry):
+        P.carry[k] = int(c)
+    P.thickComp, P.thickLo, P.thickHi = int(thickComp), float(thickLo), float(thickHi)
+    P.TComp, P.strainComp, P.TVal, P.addAngle = int(TComp), int(strainComp), float(TVal), int(bool(addAngle))
+    ctx.check(ctx.lib.pa_streamalt_run(ctx.h, len(counts), start.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(ib.ptr), C.c_void_p(sb.ptr), int(ncs),
+                                       int(nRKsteps), int(nNodes), C.byref(P), C.c_void_p(ob.ptr), C.c_void_p(bb.ptr) if bb is not None else None))
+    out = ob.to_numpy(np.float64, (nout, nNodes))
+    return out, (bb.to_numpy(np.int8, (nq, nNodes)) if bb is not None else None)
 
 
 def interpstream_fab(ctx: Context, loc: np.ndarray, loc_lo, fab: np.ndarray, fab_lo, dx, plo):

@@ -8,10 +8,24 @@
 // excluded), the upload, and both writers -- streamFile: Header (OLDFORMAT) + Elements + Level_<l>/Str_H + Str_D_00000 (VisMF),
 // outFile: <dir>/str_00000.dat (Tecplot points, stream.cpp:2228-2302).  Device side (pa_streamgrad.hip): the state of
 // stream.cpp:796-884 (FillBoundary -> FillCFgrowCells -> FillBoundary -> FixOOB) for all levels, then every line in one launch.
+//       [buildAltSurf=1 altVal=<v> [advectColdIso=0] [dt=0] [thickCompName=<c> thickLo=<v> thickHi=<v>]
+//        [strainCompName=<c> TCompName=<c> TVal=<v>] [addAngle=0] [altIsoFile=surf_new_flame.mef | surf_alt.mef]]
+// buildAltSurf (stream.cpp:973-1107): where every line meets altVal, with the seed surface's connectivity -- X Y Z, the progress
+// variable (advectColdIso: the velocities, then the progress variable) and the distance along the line there, the thermal
+// thickness, the cold-side strain and the angle to the vertical -- by pa_streamalt.hip from the lines while they are in device
+// memory; the host takes the acos of the angle's cosine, adds the input surface's distance_iso_to_alt (the reference ADDS) and
+// renames the distance to delta, or, advectColdIso, moves X by v * dt, and writes the MEF.  The mode puts the velocities among the
+// line components (needV), so into streamFile / outFile too, also when the trace follows the gradient.
 // Deviations, all stated:
-//   - buildAltSurf and everything behind it (altVal, dt, thickCompName / thickLo / thickHi, strainCompName, TCompName, TVal,
-//     addAngle, advectColdIso, altIsoFile) is not built: any of those keys aborts with a message.  So do ngpus > 1, the USE_PF
-//     variant (not compiled in the reference either) and 2-D plotfiles.
+//   - buildAltSurf=1 needs isoFile=: with seedLoc / seedRake* it aborts (a one-node "surface" is no surface).  The reference sizes
+//     the new node array by the count of lines and indexes it by node id: here every node of the trimmed surface must carry exactly
+//     one line, else the tool aborts with both counts.  nRKsteps < 3 aborts (the search and the angle index outside the line).
+//     strainCompName with TCompName found but the strain component not among the line components aborts (the reference reads
+//     component -1).  thickCompName / TCompName not among the line components: the quantity is skipped as in the reference, and one
+//     stderr line names the component.  Missing velocity components abort at once.  The reference's "Path oriented backwards" test
+//     compares a value with itself and is not built.  The other keys of the mode without buildAltSurf=1 are read by nobody, here
+//     as there.  The MEF writer takes triangles: another nodesPerElt aborts.
+//   - ngpus > 1, the USE_PF variant (not compiled in the reference either) and 2-D plotfiles abort.
 //   - A progressName that is not in the plotfile aborts at once (the reference prints "Cannot find required data in pltfile"
 //     and fails later inside FillVar).  So do a missing or doubled streamFile / outFile (the reference asserts after tracing).
 //   - Where the reference would copy an unset coarse value into a coarse-fine ghost cell inside the domain (a fine level not
@@ -49,13 +63,6 @@ int main(int argc, char** argv) {
   if (argc < 2) usage(argv[0]);
   pa::ParmParse pp(argc, argv);
   if (pp.contains("help")) usage(argv[0]);
-  for (const char* k : {"buildAltSurf", "altVal", "dt", "thickCompName", "thickLo", "thickHi", "strainCompName", "TCompName", "TVal", "addAngle",
-                        "advectColdIso", "altIsoFile"}) {
-    if (!pp.contains(k)) continue;
-    bool on = true;
-    if (std::string(k) == "buildAltSurf") pp.query(k, on);
-    if (on) pa::Abort(std::string(k) + "=: the alternate-surface path of stream.cpp (buildAltSurf) is not part of this build");
-  }
   int ngpus = 1;
   pp.query("ngpus", ngpus);
   if (ngpus > 1) pa::Abort("ngpus > 1 is not supported by stream3d (one GPU)");
@@ -79,8 +86,13 @@ int main(int argc, char** argv) {
   std::vector<int32_t> faceData;
   long long nElts = 0, nodesPerElt = 0, nSeed = 0;
   std::vector<std::string> surfNames;
+  std::vector<double> isoDist;  // the input surface's distance_iso_to_alt (buildAltSurf adds it to the new one, stream.cpp:1046-1056)
+  const std::string distanceVarName = "distance_iso_to_alt";
+  bool buildAltSurf = false;
+  pp.query("buildAltSurf", buildAltSurf);
   const int ni = pp.countval("isoFile"), ns = pp.countval("seedLoc"), nrL = pp.countval("seedRakeL"), nrR = pp.countval("seedRakeR");
   if (!((ni > 0) ^ (ns > 0) ^ ((nrL > 0) && (nrR > 0)))) pa::Abort("Assertion `ni>0 ^ ns>0 ^ (nrL>0 && nrR>0)' failed");
+  if (buildAltSurf && ni == 0) pa::Abort("buildAltSurf=1 needs isoFile=: the alternate surface takes the connectivity of a seed surface (seedLoc / seedRake* give none)");
   if (ni > 0) {
     std::string isoFile;
     pp.get("isoFile", isoFile);
@@ -95,6 +107,11 @@ int main(int argc, char** argv) {
     nodes.resize(3 * (size_t)nSeed);
     for (long long i = 0; i < nSeed; ++i)
       for (int d = 0; d < 3; ++d) nodes[(size_t)d * nSeed + i] = S.nodes[(size_t)i * nc + d];
+    for (size_t c = 0; c < nc; ++c) {  // the last component of that name, as the reference's loop leaves it
+      if (S.names[c] != distanceVarName) continue;
+      isoDist.resize((size_t)nSeed);
+      for (long long i = 0; i < nSeed; ++i) isoDist[(size_t)i] = S.nodes[(size_t)i * nc + c];
+    }
     faceData = S.conn;
   } else if (ns > 0) {
     std::vector<double> loc;
@@ -136,6 +153,12 @@ int main(int argc, char** argv) {
     for (long long i = 0; i < nSeed; ++i)
       if (idx[(size_t)i] >= 0)
         for (int d = 0; d < 3; ++d) nw[(size_t)d * nn + idx[(size_t)i]] = nodes[(size_t)d * nSeed + i];
+    if (!isoDist.empty()) {  // trim_surface keeps every component of the node FAB
+      std::vector<double> nd((size_t)nn);
+      for (long long i = 0; i < nSeed; ++i)
+        if (idx[(size_t)i] >= 0) nd[(size_t)idx[(size_t)i]] = isoDist[(size_t)i];
+      isoDist.swap(nd);
+    }
     std::vector<int32_t> nf;
     long long ne = 0;
     for (long long e = 0; e < nElts; ++e) {
@@ -151,12 +174,33 @@ int main(int argc, char** argv) {
     nElts = ne;
   }
   if (nElts <= 0) pa::Abort("no element left to write (nElts = 0)");
+  if (buildAltSurf && nodesPerElt != 3) pa::Abort("buildAltSurf: the surface writer takes triangles (nodesPerElt = " + std::to_string(nodesPerElt) + ")");
 
   // components of the state (stream.cpp:594-690)
   bool traceAlongV = false;
   pp.query("traceAlongV", traceAlongV);
+  bool needV = traceAlongV;  // the velocities among the line components; the trace follows them only with traceAlongV
+  double altVal = -1, dt = 0., thickLo = 0, thickHi = 0, TVal = 0;
+  std::string thickCompName = "null", strainCompName = "null", TCompName = "null";
+  bool addAngle = false;
+  if (buildAltSurf) {  // stream.cpp:589-610
+    pp.get("altVal", altVal);
+    pp.query("dt", dt);
+    needV = true;
+    pp.query("thickCompName", thickCompName);
+    if (thickCompName != "null") {
+      pp.get("thickLo", thickLo);
+      pp.get("thickHi", thickHi);
+    }
+    pp.query("strainCompName", strainCompName);
+    if (strainCompName != "null") {
+      pp.get("TCompName", TCompName);
+      pp.get("TVal", TVal);
+    }
+    pp.query("addAngle", addAngle);
+  }
   std::vector<std::string> inVarNames = {progressName};
-  if (traceAlongV) for (const char* v : {"x_velocity", "y_velocity", "z_velocity"}) inVarNames.push_back(v);
+  if (needV) for (const char* v : {"x_velocity", "y_velocity", "z_velocity"}) inVarNames.push_back(v);
   std::vector<int> auxComps;
   if (const int nc = pp.countval("aux_comps")) {
     pp.queryarr("aux_comps", auxComps, 0, nc);
@@ -180,11 +224,29 @@ int main(int argc, char** argv) {
   const int nCompSt = (int)inVarNames.size(), nCompStr = 3 + nCompSt;
   std::vector<std::string> strNames(surfNames.begin(), surfNames.begin() + 3);
   for (auto& n : inVarNames) strNames.push_back(n);
+  const int isoCompStr = 3, vCompStr = needV ? 4 : -1;
+  int thickComp = -1, strainComp = -1, TComp = -1;  // stream.cpp:673-698: the last line component of each name
+  for (int i = 0; i < nCompStr; ++i) {
+    if (strNames[(size_t)i] == thickCompName) thickComp = i;
+    if (strNames[(size_t)i] == strainCompName) strainComp = i;
+    if (strNames[(size_t)i] == TCompName) TComp = i;
+  }
+  if (thickComp >= 0) std::cout << "Thermal thickness component id: " << thickComp << std::endl;
+  if (strainComp >= 0) {
+    std::cout << "Strain component id: " << strainComp << std::endl;
+    std::cout << "   T component for strain eval at id: " << TComp << std::endl;
+  }
+  if (buildAltSurf) {
+    if (thickCompName != "null" && thickComp < 0) std::cerr << "thickCompName=" << thickCompName << " is not among the line components: no thermal thickness" << std::endl;
+    if (TCompName != "null" && TComp < 0) std::cerr << "TCompName=" << TCompName << " is not among the line components: no cold strain" << std::endl;
+    if (TComp >= 0 && strainComp < 0) pa::Abort("strainCompName=" + strainCompName + " is not among the line components (TCompName=" + TCompName + " is)");
+  }
 
   // trace parameters (stream.cpp:693-716)
   int nRKsteps = 51;
   pp.query("nRKsteps", nRKsteps);
   if (nRKsteps < 1) pa::Abort("nRKsteps must be at least 1");
+  if (buildAltSurf && nRKsteps < 3) pa::Abort("buildAltSurf=1 needs nRKsteps >= 3: the search and the angle index the points j = -1 .. 1 of every line");
   const int nRKh = (nRKsteps - 1) / 2;
   double hRK = 0.1;
   pp.query("hRK", hRK);
@@ -253,6 +315,41 @@ int main(int argc, char** argv) {
   }
   std::vector<double> strm((size_t)nlines * nRKsteps * nCompStr);
   std::vector<int32_t> box_flag(box_start.size() - 1, 0);
+
+  // the alternate surface (stream.cpp:973-1035): its components, and the check that the node array the reference sizes by the
+  // count of lines and indexes by node id is the trimmed surface's
+  bool advectColdIso = false;
+  std::vector<std::string> altSurfNames;
+  std::vector<double> altOut;  // [nAlt][nSeed]
+  pa_streamalt_params altP{};
+  double* daltOut = nullptr;
+  if (buildAltSurf) {
+    pp.query("advectColdIso", advectColdIso);
+    std::vector<long long> cnt((size_t)nSeed, 0);
+    bool once = nlines == nSeed;
+    for (int32_t id : ids) ++cnt[(size_t)id - 1];
+    for (long long c : cnt) once = once && c == 1;
+    if (!once)
+      pa::Abort("buildAltSurf: " + std::to_string(nlines) + " lines for " + std::to_string(nSeed) + " nodes of the surface: every node must carry exactly one line");
+    altP.isoComp = isoCompStr;
+    altP.altVal = altVal;
+    if (advectColdIso) for (int d = 0; d < 3; ++d) altP.carry[altP.ncarry++] = vCompStr + d;
+    altP.carry[altP.ncarry++] = isoCompStr;
+    altP.thickComp = thickComp;
+    altP.thickLo = thickLo;
+    altP.thickHi = thickHi;
+    altP.TComp = TComp;
+    altP.strainComp = strainComp;
+    altP.TVal = TVal;
+    altP.addAngle = addAngle ? 1 : 0;
+    for (int d = 0; d < 3; ++d) altSurfNames.push_back(strNames[(size_t)d]);
+    for (int k = 0; k < altP.ncarry; ++k) altSurfNames.push_back(strNames[(size_t)altP.carry[k]]);
+    altSurfNames.push_back(distanceVarName);
+    if (thickComp >= 0) altSurfNames.push_back(advectColdIso ? "thermalThickness" : "thermalThickness_notAdv");
+    if (TComp >= 0) altSurfNames.push_back("coldStrain");
+    if (addAngle) altSurfNames.push_back("angleWRTvert");
+    altOut.resize(altSurfNames.size() * (size_t)nSeed);
+  }
   {
     pa::Ctx ctx;
     std::vector<std::unique_ptr<pa::DevLevel>> dl;
@@ -277,7 +374,16 @@ int main(int argc, char** argv) {
       ctx.check(pa_memcpy_h2d(ctx.h, dnodes, nodes.data(), (int64_t)nodes.size() * 8));
       ctx.check(pa_memcpy_h2d(ctx.h, dids, ids.data(), (int64_t)ids.size() * 4));
     }
+    if (buildAltSurf) {
+      daltOut = (double*)pa_device_malloc(ctx.h, (int64_t)altOut.size() * 8);
+      if (!daltOut) pa::Abort(pa_last_error(ctx.h));
+    }
     ctx.check(pa_streamgrad_trace(ctx.h, Nlev, st.data(), traceAlongV ? 1 : -1, nSeed, dnodes, box_start.data(), dids, nRKsteps, hRK, dstrm, box_flag.data()));
+    if (buildAltSurf) {  // every quantity of the new surface from the lines in device memory, node-ordered
+      ctx.check(pa_streamalt_run(ctx.h, (int32_t)(box_start.size() - 1), box_start.data(), dids, dstrm, nCompStr, nRKsteps, nSeed, &altP, daltOut, nullptr));
+      ctx.check(pa_memcpy_d2h(ctx.h, altOut.data(), daltOut, (int64_t)altOut.size() * 8));
+      pa_device_free(ctx.h, daltOut);
+    }
     if (nlines > 0) {
       ctx.check(pa_memcpy_d2h(ctx.h, strm.data(), dstrm, (int64_t)strm.size() * 8));
       pa_device_free(ctx.h, dnodes);
@@ -346,6 +452,41 @@ int main(int argc, char** argv) {
           }
         }
     }
+  }
+
+  if (buildAltSurf) {  // stream.cpp:973-1107; the messages of build_surface_at_isoVal and the add_* functions in their order
+    if (verbose > 0) std::cout << "building new surface where " << strNames[(size_t)isoCompStr] << " = " << altVal << std::endl;
+    for (int lev = 0; lev < Nlev; ++lev) std::cerr << "building new surface at level: " << lev << std::endl;
+    std::cerr << "New surface built, communicating info to ioproc " << std::endl;
+    std::cerr << "Data sent, building new iso" << std::endl;
+    std::cerr << "New iso built on ioproc " << std::endl;
+    if (thickComp >= 0) std::cerr << "Thermal thickness computed, communicating info to ioproc " << std::endl << "New surface data added on ioproc " << std::endl;
+    if (TComp >= 0) std::cerr << "Cold Strain computed, communicating info to ioproc " << std::endl << "New surface data added on ioproc " << std::endl;
+    if (addAngle) std::cerr << "Angle computed, communicating info to ioproc " << std::endl << "New surface data added on ioproc " << std::endl;
+    const size_t nAlt = altSurfNames.size(), N = (size_t)nSeed;
+    if (addAngle) {  // the kernel leaves the cosine (add_angle_to_surf :1265)
+      double* a = altOut.data() + (nAlt - 1) * N;
+      for (size_t i = 0; i < N; ++i) a[i] = std::acos(a[i]);
+    }
+    if (!advectColdIso) {  // :1041-1060: the input surface's distance is ADDED to the new one, which is renamed in any case
+      const size_t dCompAlt = 3 + (size_t)altP.ncarry;
+      if (!isoDist.empty())
+        for (size_t i = 0; i < N; ++i) altOut[dCompAlt * N + i] += isoDist[i];
+      altSurfNames[dCompAlt] = "delta";
+    } else {  // :1061-1084: X += v * dt, the velocities are the first carried components
+      for (size_t i = 0; i < N; ++i)
+        for (size_t d = 0; d < 3; ++d) altOut[d * N + i] += altOut[(3 + d) * N + i] * dt;
+    }
+    std::string altIsoFile = advectColdIso ? "surf_alt.mef" : "surf_new_flame.mef";
+    const std::string label = advectColdIso ? "advected alt surface" : "new flame surface from advected alt";
+    pp.query("altIsoFile", altIsoFile);
+    std::vector<double> tn(nAlt * N);  // write_iso (:1166-1209): component fastest
+    for (size_t i = 0; i < N; ++i)
+      for (size_t c = 0; c < nAlt; ++c) tn[i * nAlt + c] = altOut[c * N + i];
+    std::vector<int32_t> elts0(faceData.size());
+    for (size_t q = 0; q < faceData.size(); ++q) elts0[q] = faceData[q] - 1;
+    pa::write_mef(altIsoFile, label, altSurfNames, tn, elts0);
+    std::cerr << "Finished writing streamline data " << std::endl;
   }
   return 0;
 }
