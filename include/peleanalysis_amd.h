@@ -903,6 +903,41 @@ int pa_plane_minmax(pa_ctx*, const pa_plane*, int comp, double* mn, double* mx);
 int pa_plane_pixelize(pa_ctx*, const pa_plane*, int comp, double mn, double mx, uint8_t* levels);
 void pa_plane_destroy(pa_plane*);
 
+/* ------------------------------------------------------------- quadric edge-collapse decimation of a surface (decimateMEF.cpp)
+ * The job of the reference's qslim wrapper (Tools/qslim/main.cpp: read_mef :323-359, slim_init :92-136, output_mef :214-263; slim->decimate, Tools/qslim/qslim.cpp:58)
+ * with an algorithm of our own (mixkit is not part of the reference tree): rounds that contract an independent set of
+ * the cheapest edges at once.  Positions stay double (the reference casts to float) and the contraction order is not qslim's.
+ * NUMERICS: every floating-point value is computed by one thread in a written order, without fused multiply-adds; lane groups and
+ * atomics only combine flags, integer counts and minima of unique 64-bit integer keys.  The same input gives the same bytes, and
+ * they are the bytes of the restatement tests/decimate_ref.py after every round.  One GPU.  All arrays are HOST memory; every call
+ * is synchronous. */
+typedef struct pa_decimate pa_decimate;
+/* decimateMEF.cpp (Tools/qslim/main.cpp:323-359 read_mef, :92-136 slim_init): xyz [nnodes][3]; elts [nelts][3], 1-based.
+ * boundary_weight / weighting (0 uniform, 1 area) / placement (0 endpoints, 1 endpoints or midpoint, 3 optimal): -B, -W, -O of
+ * Tools/qslim/cmdline.cpp:23-45.  NULL (and pa_last_error) for a node id outside 1 .. nnodes, an element that names a node twice, any
+ * other weighting or placement, or more than 2^31 - 1 nodes or 3 * nelts (the bound on the edges) */
+pa_decimate* pa_decimate_create(pa_ctx*, int64_t nnodes, const double* xyz, int64_t nelts, const int32_t* elts, double boundary_weight, int weighting,
+                                int placement);
+/* decimateMEF.cpp: ONE round towards face_target (part of slim->decimate(face_target), Tools/qslim/qslim.cpp:58).  1 = a round was
+ * applied; 0 = nothing left to do (the target is reached, or no edge passes the tests: pa_decimate_last_round says which); -1 = error */
+int pa_decimate_round(pa_ctx*, pa_decimate*, int64_t face_target);
+/* decimateMEF.cpp: rounds until one returns 0, at most max_rounds of them (slim->decimate, Tools/qslim/qslim.cpp:58); the number of
+ * rounds applied, or -1.  The surface ends with face_target or face_target - 1 faces unless no valid contraction is left. */
+int pa_decimate_run(pa_ctx*, pa_decimate*, int64_t face_target, int max_rounds);
+/* decimateMEF.cpp (one record per round; the reference reports nothing between Tools/qslim/qslim.cpp:49 and :60): edges, locked edges,
+ * candidates, budget = ceil((valid faces - target) / 2), selected, applied, faces removed, valid faces afterwards */
+int pa_decimate_last_round(const pa_decimate*, int64_t rec[8]);
+/* decimateMEF.cpp (the "(<v>v/<f>f)" of Tools/qslim/qslim.cpp:49-61): vertices the valid faces use, valid faces, rounds applied */
+int pa_decimate_counts(const pa_decimate*, int64_t* nverts, int64_t* nfaces, int64_t* rounds);
+/* decimateMEF.cpp (output_mef, Tools/qslim/main.cpp:214-263): xyz [nverts][3] of the used vertices and elts [nfaces][3], 1-based, of the
+ * valid faces, both in input order */
+int pa_decimate_read(pa_ctx*, const pa_decimate*, double* xyz, int32_t* elts);
+/* decimateMEF.cpp: the whole state, for comparing a round on its own: xyz_all [nnodes][3], faces_all [nelts][3] 0-based (a dead face
+ * keeps its slot and its last vertices), face_valid [nelts], quadrics [10][nnodes] (q11 q12 q13 q14 q22 q23 q24 q33 q34 q44).  Any
+ * pointer may be NULL. */
+int pa_decimate_read_state(pa_ctx*, const pa_decimate*, double* xyz_all, int32_t* faces_all, uint8_t* face_valid, double* quadrics);
+void pa_decimate_destroy(pa_decimate*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -260,6 +260,14 @@ def load_library() -> C.CDLL:
         "pa_plane_minmax": (C.c_int, [vp, vp, C.c_int, pdbl, pdbl]),
         "pa_plane_pixelize": (C.c_int, [vp, vp, C.c_int, dbl, dbl, C.POINTER(C.c_uint8)]),
         "pa_plane_destroy": (None, [vp]),
+        "pa_decimate_create": (vp, [vp, i64, pdbl, i64, pi32, dbl, C.c_int, C.c_int]),
+        "pa_decimate_round": (C.c_int, [vp, vp, i64]),
+        "pa_decimate_run": (C.c_int, [vp, vp, i64, C.c_int]),
+        "pa_decimate_last_round": (C.c_int, [vp, C.POINTER(i64)]),
+        "pa_decimate_counts": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+        "pa_decimate_read": (C.c_int, [vp, vp, pdbl, pi32]),
+        "pa_decimate_read_state": (C.c_int, [vp, vp, pdbl, pi32, C.POINTER(C.c_uint8), pdbl]),
+        "pa_decimate_destroy": (None, [vp]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -1371,6 +1379,81 @@ class SurfBin:
         self.ctx.check(self.ctx.lib.pa_surfbin_read(self.ctx.h, self.h, area.ctypes.data_as(C.POINTER(C.c_double)), hits.ctypes.data_as(p64), C.byref(tot),
                                                     C.byref(outside), cnt.ctypes.data_as(p64)))
         return area, hits, tot.value, outside.value, dict(zip(self.COUNTERS, (int(v) for v in cnt)))
+
+
+class Decimate:
+    """quadric edge-collapse decimation of a triangulated surface (decimateMEF.cpp; pa_decimate_*): xyz [N][3], elts [M][3] 1-based;
+    weighting 0 uniform / 1 area, placement 0 endpoints / 1 endpoints or midpoint / 3 optimal.  `fill` (tests): the 64-bit pattern the
+    output arrays of read / read_state hold before the call"""
+
+    RECORD = ("edges", "locked", "candidates", "budget", "selected", "applied", "faces_removed", "valid_faces")
+
+    def __init__(self, ctx: Context, xyz, elts, boundary_weight: float = 1000.0, weighting: int = 1, placement: int = 3):
+        self.ctx = ctx
+        x = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64)[:, :3])
+        e = np.ascontiguousarray(elts, dtype=np.int32).reshape(-1, 3)
+        self.nnodes, self.nelts = len(x), len(e)
+        self.h = ctx.lib.pa_decimate_create(ctx.h, len(x), x.ctypes.data_as(C.POINTER(C.c_double)), len(e), e.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            float(boundary_weight), int(weighting), int(placement))
+        if not self.h:
+            raise PaError(ctx.lib.pa_last_error(ctx.h).decode())
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.pa_decimate_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _rc(self, rc: int) -> int:
+        if rc < 0:
+            raise PaError(self.ctx.lib.pa_last_error(self.ctx.h).decode())
+        return rc
+
+    def round(self, face_target: int) -> bool:
+        """one round; False when nothing is left to do"""
+        return self._rc(self.ctx.lib.pa_decimate_round(self.ctx.h, self.h, int(face_target))) == 1
+
+    def run(self, face_target: int, max_rounds: int = 1000000) -> int:
+        return self._rc(self.ctx.lib.pa_decimate_run(self.ctx.h, self.h, int(face_target), int(max_rounds)))
+
+    def last_round(self):
+        rec = np.zeros(8, dtype=np.int64)
+        self.ctx.check(self.ctx.lib.pa_decimate_last_round(self.h, rec.ctypes.data_as(C.POINTER(C.c_int64))))
+        return [int(v) for v in rec]
+
+    def counts(self):
+        """(vertices in use, valid faces, rounds applied)"""
+        v, f, r = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self.ctx.check(self.ctx.lib.pa_decimate_counts(self.h, C.byref(v), C.byref(f), C.byref(r)))
+        return v.value, f.value, r.value
+
+    @staticmethod
+    def _out(shape, dtype, fill):
+        a = np.zeros(shape, dtype=dtype)
+        if fill is not None:
+            raw = np.frombuffer(np.uint64(fill).tobytes(), dtype=np.uint8)
+            a.view(np.uint8).reshape(-1)[:] = np.resize(raw, a.nbytes)
+        return a
+
+    def read(self, fill=None):
+        """(xyz [nverts][3], elts [nfaces][3] int32, 1-based)"""
+        nv, nf, _ = self.counts()
+        xyz, elts = self._out((nv, 3), np.float64, fill), self._out((nf, 3), np.int32, fill)
+        self.ctx.check(self.ctx.lib.pa_decimate_read(self.ctx.h, self.h, xyz.ctypes.data_as(C.POINTER(C.c_double)), elts.ctypes.data_as(C.POINTER(C.c_int32))))
+        return xyz, elts
+
+    def read_state(self, fill=None):
+        """(xyz_all [N][3], faces_all [M][3] int32 0-based, face_valid [M] uint8, quadrics [10][N])"""
+        xyz, faces = self._out((self.nnodes, 3), np.float64, fill), self._out((self.nelts, 3), np.int32, fill)
+        valid, quad = self._out((self.nelts,), np.uint8, fill), self._out((10, self.nnodes), np.float64, fill)
+        self.ctx.check(self.ctx.lib.pa_decimate_read_state(self.ctx.h, self.h, xyz.ctypes.data_as(C.POINTER(C.c_double)), faces.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                           valid.ctypes.data_as(C.POINTER(C.c_uint8)), quad.ctypes.data_as(C.POINTER(C.c_double))))
+        return xyz, faces, valid, quad
 
 
 class FeMesh:
