@@ -938,6 +938,56 @@ int pa_decimate_read(pa_ctx*, const pa_decimate*, double* xyz, int32_t* elts);
 int pa_decimate_read_state(pa_ctx*, const pa_decimate*, double* xyz_all, int32_t* faces_all, uint8_t* face_valid, double* quadrics);
 void pa_decimate_destroy(pa_decimate*);
 
+/* ------------------------------------------------------------- cutting and trimming a surface (sliceMEF.cpp, trimMEFgen.cpp)
+ * A pa_surf is a triangulated surface with its node fields that stays in device memory between steps (component-major columns,
+ * 0-based triples: DESIGN.md 3.15), so trim -> area -> slice -> slice runs without an upload in between.
+ * NUMERICS: every floating-point value is computed by one thread in a written order, without fused multiply-adds; atomics and lane
+ * groups combine only flags, integer counts, minima / maxima of bit patterns and fixed-point limbs.  The same input gives the same
+ * bytes, and they are the bytes of the restatement tests/surfcut_ref.py.  The one value that is not the reference's: the area TOTAL is
+ * the exactly rounded 192-bit fixed-point sum of the triangle areas (scaled from the largest, rounded once), where the reference adds
+ * serially in element order (trimMEFgen.cpp:64-85).  One GPU.  All arrays are HOST memory; every call is synchronous. */
+typedef struct pa_surf pa_surf;
+/* sliceMEF.cpp:204-237 / trimMEFgen.cpp:423-429 (read_iso and the copy into GridPts): nodes [nnodes][ncomp] node-major as the file
+ * stores them, elts [nelts][3] 1-based, triangles only.  NULL (and pa_last_error) for a node id outside 1 .. nnodes ("element <n>
+ * names a node that does not exist"), ncomp < 3, or more than 2^31 - 1 nodes or 3 * nelts */
+pa_surf* pa_surf_create(pa_ctx*, int64_t nnodes, int ncomp, const double* nodes, int64_t nelts, const int32_t* elts);
+/* nodes.box().length(0), nElts, nodes.nComp() (sliceMEF.cpp:212-213, :230) of the surface as it stands (after a trim: the trimmed one) */
+int pa_surf_counts(const pa_surf*, int64_t* nnodes, int64_t* nelts, int* ncomp);
+/* write_iso's arguments (trimMEFgen.cpp:526): nodes [nnodes][ncomp], elts [nelts][3] 1-based.  Either pointer may be NULL.  The
+ * surface is not changed, but the handle's scratch buffers are used (hence no const): one call at a time per handle. */
+int pa_surf_read(pa_ctx*, pa_surf*, double* nodes, int32_t* elts);
+/* sliceMEF.cpp:239-256 (the element loop), :637-681 (Segmentise), :607-630 (VertexInterp), :581-605 (VI_doIt), :260-268 (numbering):
+ * the contour value[comp] == val.  Bit q of an element's case is set where node q has value[comp] < val (strict); cases 0 and 7 give
+ * nothing, every other case ONE segment whose ends lie on the edges (apex, other) -- 1/6: (p0,p1),(p0,p2); 2/5: (p1,p0),(p1,p2);
+ * 3/4: (p2,p0),(p2,p1) -- in element order.  A vertex lives under the DIRECTED pair of the first request for it (requests ordered by
+ * element, then first or second end: the reference's map orders by std::pair's <, and the reverse lookup of :614 joins (a,b) and
+ * (b,a)); its value is VI_doIt in that direction; vertices are numbered in lexicographic order of that pair.  The surface is not
+ * changed and nothing is uploaded; the result stays on the device until the next slice or trim of this handle. */
+int pa_surf_slice(pa_ctx*, pa_surf*, int comp, double val, int64_t* nverts, int64_t* nsegs);
+/* the last slice (sliceMEF.cpp:260-268 vertVec, :429-436 slice_segs): verts [nverts][ncomp]; pairs [nverts][2] the directed node pair
+ * (0-based) of each vertex; segs [nsegs][2] vertex ids (0-based; the file adds 1); src_elt [nsegs] the element (0-based) of each
+ * segment; the incidence CSR the line assembly needs (:270-309, FindMySeg :537-546): csr_off [nverts + 1], csr_adj [2 * nsegs] = the
+ * segments of each vertex in ascending segment index.  Any pointer may be NULL. */
+int pa_surf_slice_read(pa_ctx*, const pa_surf*, double* verts, int32_t* pairs, int32_t* segs, int32_t* src_elt, int32_t* csr_off, int32_t* csr_adj);
+/* trimMEFgen.cpp:90-192 (trim_surface), :195-294 (trim_surface_RXY), :297-372 (remove_unused_nodes) in one step: a node is removed if
+ * ANY of the ncond conditions value[comps[i]] <ops[i]> vals[i] holds (ops: 0 lt, 1 le, 2 gt, 3 ge, 4 eq), or, when rxy >= 0, if
+ * sqrt(x*x + y*y) <rxy_op> rxy holds; an element survives only if all three of its nodes do; nodes that no surviving element uses are
+ * removed as well (*nodes_unused: how many of those the conditions had kept, the "Removed <n> unusued nodes" of :370).  Nodes and
+ * elements keep their input order; ids are renumbered.  The handle is replaced in place; a slice it held is dropped. */
+int pa_surf_trim(pa_ctx*, pa_surf*, int ncond, const int32_t* comps, const int32_t* ops, const double* vals, double rxy, int rxy_op, int64_t* nodes_unused);
+/* trimMEFgen.cpp:53-87 (surface_area), :375-409 (triangle_area), :511-518 (min, max): every triangle's area by the written expression
+ * 0.5 * sqrt(t0*t0 + t1*t1 + t2*t2); *total = their exactly rounded sum (see NUMERICS), *amin / *amax the smallest / largest (all 0 for
+ * a surface without elements).  Fails when an area is not finite.  Any pointer may be NULL.  The surface and a slice it holds are
+ * not changed, but the handle's scratch and launch record are written (hence no const): one call at a time per handle. */
+int pa_surf_area(pa_ctx*, pa_surf*, double* total, double* amin, double* amax);
+/* what the last slice, trim or area call of this handle launched, for tests (the reference has no counterpart; sliceMEF.cpp:257 and
+ * trimMEFgen.cpp:370 are its only reports).  rec[0] = 1 slice / 2 trim / 3 area, rec[7] = kernels launched (scans and sorts not counted).
+ * slice: [1] elements classified, [2] segments, [3] requests sorted, [4] vertices, [5] values interpolated, [6] CSR entries;
+ * trim: [1] nodes flagged, [2] elements flagged, [3] nodes the conditions kept, [4] nodes out, [5] elements out, [6] values gathered;
+ * area: [1] elements, [2] terms added in fixed point. */
+int pa_surf_last_launch(const pa_surf*, int64_t rec[8]);
+void pa_surf_destroy(pa_surf*);
+
 #ifdef __cplusplus
 }
 #endif

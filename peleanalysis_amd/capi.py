@@ -268,6 +268,15 @@ def load_library() -> C.CDLL:
         "pa_decimate_read": (C.c_int, [vp, vp, pdbl, pi32]),
         "pa_decimate_read_state": (C.c_int, [vp, vp, pdbl, pi32, C.POINTER(C.c_uint8), pdbl]),
         "pa_decimate_destroy": (None, [vp]),
+        "pa_surf_create": (vp, [vp, i64, C.c_int, pdbl, i64, pi32]),
+        "pa_surf_counts": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int)]),
+        "pa_surf_read": (C.c_int, [vp, vp, pdbl, pi32]),
+        "pa_surf_slice": (C.c_int, [vp, vp, C.c_int, dbl, C.POINTER(i64), C.POINTER(i64)]),
+        "pa_surf_slice_read": (C.c_int, [vp, vp, pdbl, pi32, pi32, pi32, pi32, pi32]),
+        "pa_surf_trim": (C.c_int, [vp, vp, C.c_int, pi32, pi32, pdbl, dbl, C.c_int, C.POINTER(i64)]),
+        "pa_surf_area": (C.c_int, [vp, vp, pdbl, pdbl, pdbl]),
+        "pa_surf_last_launch": (C.c_int, [vp, C.POINTER(i64)]),
+        "pa_surf_destroy": (None, [vp]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -1381,6 +1390,15 @@ class SurfBin:
         return area, hits, tot.value, outside.value, dict(zip(self.COUNTERS, (int(v) for v in cnt)))
 
 
+def _out_array(shape, dtype, fill):
+    """an output array for a read-back; `fill` (tests): the 64-bit pattern every 8 bytes of it hold before the call"""
+    a = np.zeros(shape, dtype=dtype)
+    if fill is not None:
+        raw = np.frombuffer(np.uint64(fill).tobytes(), dtype=np.uint8)
+        a.view(np.uint8).reshape(-1)[:] = np.resize(raw, a.nbytes)
+    return a
+
+
 class Decimate:
     """quadric edge-collapse decimation of a triangulated surface (decimateMEF.cpp; pa_decimate_*): xyz [N][3], elts [M][3] 1-based;
     weighting 0 uniform / 1 area, placement 0 endpoints / 1 endpoints or midpoint / 3 optimal.  `fill` (tests): the 64-bit pattern the
@@ -1432,13 +1450,7 @@ class Decimate:
         self.ctx.check(self.ctx.lib.pa_decimate_counts(self.h, C.byref(v), C.byref(f), C.byref(r)))
         return v.value, f.value, r.value
 
-    @staticmethod
-    def _out(shape, dtype, fill):
-        a = np.zeros(shape, dtype=dtype)
-        if fill is not None:
-            raw = np.frombuffer(np.uint64(fill).tobytes(), dtype=np.uint8)
-            a.view(np.uint8).reshape(-1)[:] = np.resize(raw, a.nbytes)
-        return a
+    _out = staticmethod(_out_array)
 
     def read(self, fill=None):
         """(xyz [nverts][3], elts [nfaces][3] int32, 1-based)"""
@@ -1454,6 +1466,103 @@ class Decimate:
         self.ctx.check(self.ctx.lib.pa_decimate_read_state(self.ctx.h, self.h, xyz.ctypes.data_as(C.POINTER(C.c_double)), faces.ctypes.data_as(C.POINTER(C.c_int32)),
                                                            valid.ctypes.data_as(C.POINTER(C.c_uint8)), quad.ctypes.data_as(C.POINTER(C.c_double))))
         return xyz, faces, valid, quad
+
+
+class Surf:
+    """a triangulated surface with its node fields, kept on the device (sliceMEF.cpp, trimMEFgen.cpp; pa_surf_*): nodes [N][ncomp >= 3],
+    elts [M][3] 1-based.  slice / trim / area work on the handle, trim replaces it in place.  `fill` (tests): the 64-bit pattern the
+    output arrays of read / slice_read hold before the call"""
+
+    OPS = {"lt": 0, "le": 1, "gt": 2, "ge": 3, "eq": 4}
+    LAUNCH = {1: ("slice", "elements", "segments", "requests", "vertices", "values", "csr_entries", "kernels"),
+              2: ("trim", "nodes", "elements", "nodes_kept", "nodes_out", "elements_out", "values", "kernels"),
+              3: ("area", "elements", "terms", None, None, None, None, "kernels")}
+
+    def __init__(self, ctx: Context, nodes, elts):
+        self.ctx = ctx
+        x = np.ascontiguousarray(nodes, dtype=np.float64)
+        if x.ndim != 2:
+            raise PaError("Surf: nodes must be [N][ncomp]")
+        e = np.ascontiguousarray(elts, dtype=np.int32).reshape(-1, 3)
+        self.h = ctx.lib.pa_surf_create(ctx.h, x.shape[0], x.shape[1], x.ctypes.data_as(C.POINTER(C.c_double)), len(e), e.ctypes.data_as(C.POINTER(C.c_int32)))
+        if not self.h:
+            raise PaError(ctx.lib.pa_last_error(ctx.h).decode())
+        self.nverts = self.nsegs = 0
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.pa_surf_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def counts(self):
+        """(nodes, elements, components)"""
+        n, m, c = C.c_int64(0), C.c_int64(0), C.c_int(0)
+        self.ctx.check(self.ctx.lib.pa_surf_counts(self.h, C.byref(n), C.byref(m), C.byref(c)))
+        return n.value, m.value, c.value
+
+    def read(self, fill=None):
+        """(nodes [N][ncomp], elts [M][3] int32, 1-based)"""
+        n, m, c = self.counts()
+        nodes, elts = _out_array((n, c), np.float64, fill), _out_array((m, 3), np.int32, fill)
+        self.ctx.check(self.ctx.lib.pa_surf_read(self.ctx.h, self.h, nodes.ctypes.data_as(C.POINTER(C.c_double)), elts.ctypes.data_as(C.POINTER(C.c_int32))))
+        return nodes, elts
+
+    def slice(self, comp: int, val: float):
+        """the contour value[comp] == val; -> (vertices, segments)"""
+        nv, ns = C.c_int64(0), C.c_int64(0)
+        self.ctx.check(self.ctx.lib.pa_surf_slice(self.ctx.h, self.h, int(comp), float(val), C.byref(nv), C.byref(ns)))
+        self.nverts, self.nsegs = nv.value, ns.value
+        return self.nverts, self.nsegs
+
+    def slice_read(self, fill=None):
+        """(verts [nverts][ncomp], pairs [nverts][2], segs [nsegs][2], src_elt [nsegs], csr_off [nverts + 1], csr_adj [2 nsegs]); ids 0-based"""
+        nv, ns, nc = self.nverts, self.nsegs, self.counts()[2]
+        o = _out_array
+        verts, pairs, segs = o((nv, nc), np.float64, fill), o((nv, 2), np.int32, fill), o((ns, 2), np.int32, fill)
+        src, off, adj = o((ns,), np.int32, fill), o((nv + 1,), np.int32, fill), o((2 * ns,), np.int32, fill)
+        p32 = C.POINTER(C.c_int32)
+        self.ctx.check(self.ctx.lib.pa_surf_slice_read(self.ctx.h, self.h, verts.ctypes.data_as(C.POINTER(C.c_double)), pairs.ctypes.data_as(p32), segs.ctypes.data_as(p32),
+                                                       src.ctypes.data_as(p32), off.ctypes.data_as(p32), adj.ctypes.data_as(p32)))
+        return verts, pairs, segs, src, off, adj
+
+    def trim(self, conds=(), rxy: float = -1.0, sign_rxy: str = "lt") -> int:
+        """conds: (comp, "lt" | "le" | "gt" | "ge" | "eq", val) ...; -> the nodes removed because no surviving element uses them"""
+        for _, op, _ in conds:
+            if op not in self.OPS:
+                raise PaError("Bad signs data. Use one of [lt,le,gt,ge,eq]")
+        if rxy >= 0 and sign_rxy not in self.OPS:
+            raise PaError("Bad sign data.  Use one of [lt,le,gt,ge,eq]")
+        n = len(conds)
+        cc = (C.c_int32 * max(n, 1))(*[int(c[0]) for c in conds])
+        oo = (C.c_int32 * max(n, 1))(*[self.OPS[c[1]] for c in conds])
+        vv = (C.c_double * max(n, 1))(*[float(c[2]) for c in conds])
+        unused = C.c_int64(0)
+        self.ctx.check(self.ctx.lib.pa_surf_trim(self.ctx.h, self.h, n, cc, oo, vv, float(rxy), self.OPS.get(sign_rxy, 0), C.byref(unused)))
+        self.nverts = self.nsegs = 0
+        return unused.value
+
+    def area(self):
+        """(total, smallest, largest triangle area)"""
+        t, lo, hi = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        self.ctx.check(self.ctx.lib.pa_surf_area(self.ctx.h, self.h, C.byref(t), C.byref(lo), C.byref(hi)))
+        return t.value, lo.value, hi.value
+
+    def last_launch(self):
+        """{"op": "slice" | "trim" | "area", <item name>: count ...} of the last call"""
+        rec = np.zeros(8, dtype=np.int64)
+        self.ctx.check(self.ctx.lib.pa_surf_last_launch(self.h, rec.ctypes.data_as(C.POINTER(C.c_int64))))
+        names = self.LAUNCH.get(int(rec[0]))
+        if names is None:
+            return {"op": None}
+        out = {"op": names[0]}
+        out.update({k: int(v) for k, v in zip(names[1:], rec[1:]) if k})
+        return out
 
 
 class FeMesh:
