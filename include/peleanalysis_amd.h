@@ -984,9 +984,47 @@ int pa_surf_area(pa_ctx*, pa_surf*, double* total, double* amin, double* amax);
  * trimMEFgen.cpp:370 are its only reports).  rec[0] = 1 slice / 2 trim / 3 area, rec[7] = kernels launched (scans and sorts not counted).
  * slice: [1] elements classified, [2] segments, [3] requests sorted, [4] vertices, [5] values interpolated, [6] CSR entries;
  * trim: [1] nodes flagged, [2] elements flagged, [3] nodes the conditions kept, [4] nodes out, [5] elements out, [6] values gathered;
- * area: [1] elements, [2] terms added in fixed point. */
+ * area: [1] elements, [2] terms added in fixed point.
+ * rec[0] = 4 merge / 5 scale / 6 product / 7 select (below).  merge: [1] nodes of S, [2] nodes of M entered in the table (0 off the grid
+ * path), [3] path taken: 0 append, 1 grid, 2 brute force, [4] duplicates found, [5] nodes appended, [6] elements appended;
+ * scale, product, select: [1] values written. */
 int pa_surf_last_launch(const pa_surf*, int64_t rec[8]);
 void pa_surf_destroy(pa_surf*);
+
+/* ------------------------------------------------------------- joining surfaces (mergeMEF.cpp, scaleMEF.cpp, multMEF.cpp, combineMEF.cpp)
+ * The same handle: merge -> scale -> select -> trim -> slice runs without leaving the device.  NUMERICS as above: one
+ * thread per value in a written order, no fused multiply-adds; atomics combine only integer counts, minima and maxima.  The bytes are
+ * those of the restatement tests/surfjoin_ref.py.  Handles from product and select may have fewer than three components: they can be
+ * read, sliced, scaled, selected from and trimmed by conditions, while pa_surf_area, pa_surf_trim with rxy >= 0 and pa_surfjoin_merge
+ * with rem_dup_nodes refuse them. */
+/* mergeMEF.cpp:138-244 (merge_iso): S is merged into M.  With rem_dup_nodes = 0 (the reference's default, :74) nothing is compared and
+ * node i of S becomes node nN_M + i.  With rem_dup_nodes = 1 node i of S becomes the SMALLEST j < nN_M (the count before this call:
+ * nodes of S are never compared with each other) for which ((dx0*dx0) + dx1*dx1) + dx2*dx2 <= eps*eps holds (:186-208; dx = S minus M,
+ * eps*eps formed once, :184); a comparison with a NaN is false, so NaN and +-inf coordinates never match; a node without such a j gets
+ * the next new id in order of i.  If no node of S is new (cnt == nNodesM, :210) NOTHING is appended -- the reference drops the elements
+ * of S as well, and so does this call -- and *appended = 0; otherwise the new nodes are appended with all their components in S's
+ * order (M's own values win at a duplicate), all elements of S are appended after M's, renumbered, degenerate and repeated ones as they
+ * are (:229-242), and *appended = 1.  method: 0 auto, 1 the hashed cell grid, 2 brute force (the reference's loop); both give the same
+ * bytes.  The grid is taken only where it is provably conservative (pa_surfjoin.hip): auto takes brute force, and method = 1 refuses,
+ * where a cell coordinate of M or S reaches 2^51 or is not finite, where M has no finite node, or where fewer than 2 cells span M (eps
+ * at or above its extent).  M is replaced in place; a call that succeeds drops a slice M held (also where nothing was appended).
+ * Refused: different component counts, eps*eps not finite, a result of more than 2^31 - 1 nodes or 3 * nelts, S == M, rem_dup_nodes
+ * with fewer than three components, method = 1 where the grid cannot be taken.  A refused or failed call leaves M as it was: nodes,
+ * elements, the slice it held and its launch record. */
+int pa_surfjoin_merge(pa_ctx*, pa_surf* M, const pa_surf* S, double eps, int rem_dup_nodes, int method, int* appended);
+/* scaleMEF.cpp:101-108: value[comps[k]] = value[comps[k]] * vals[k] at every node, for k = 0 .. n - 1 in list order; a component named
+ * twice is scaled twice, (d * v0) * v1.  In place; a slice the handle held is dropped. */
+int pa_surfjoin_scale(pa_ctx*, pa_surf*, int n, const int32_t* comps, const double* vals);
+/* multMEF.cpp:135-148: a NEW handle of one component, ((1.0 * d[comps[0]]) * d[comps[1]]) * ..., with the elements of the surface;
+ * n = 1 .. 32, repeats allowed.  NULL (and pa_last_error) on a component out of range.  Destroy it with pa_surf_destroy.  The launch
+ * record is the NEW handle's; the source is not touched. */
+pa_surf* pa_surfjoin_product(pa_ctx*, const pa_surf*, int n, const int32_t* comps);
+/* combineMEF.cpp:165-181: a NEW handle of nsel components, column k a copy of component comps[k] of L (which[k] = 0) or of R
+ * (which[k] = 1), in the given order, repeats allowed, with the elements of L.  R may be NULL when every which[k] is 0.  NULL (and
+ * pa_last_error) where the element counts differ ("MEF files not compible", :117-120) and -- a deviation: the reference copies over the
+ * intersection of the two boxes and leaves the rest uninitialised -- where the node counts differ.  The launch record is the NEW
+ * handle's; L and R are not touched. */
+pa_surf* pa_surfjoin_select(pa_ctx*, const pa_surf* L, const pa_surf* R_or_null, int nsel, const int32_t* which, const int32_t* comps);
 
 #ifdef __cplusplus
 }

@@ -277,6 +277,10 @@ def load_library() -> C.CDLL:
         "pa_surf_area": (C.c_int, [vp, vp, pdbl, pdbl, pdbl]),
         "pa_surf_last_launch": (C.c_int, [vp, C.POINTER(i64)]),
         "pa_surf_destroy": (None, [vp]),
+        "pa_surfjoin_merge": (C.c_int, [vp, vp, vp, dbl, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+        "pa_surfjoin_scale": (C.c_int, [vp, vp, C.c_int, pi32, pdbl]),
+        "pa_surfjoin_product": (vp, [vp, vp, C.c_int, pi32]),
+        "pa_surfjoin_select": (vp, [vp, vp, vp, C.c_int, pi32, pi32]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -1476,7 +1480,12 @@ class Surf:
     OPS = {"lt": 0, "le": 1, "gt": 2, "ge": 3, "eq": 4}
     LAUNCH = {1: ("slice", "elements", "segments", "requests", "vertices", "values", "csr_entries", "kernels"),
               2: ("trim", "nodes", "elements", "nodes_kept", "nodes_out", "elements_out", "values", "kernels"),
-              3: ("area", "elements", "terms", None, None, None, None, "kernels")}
+              3: ("area", "elements", "terms", None, None, None, None, "kernels"),
+              4: ("merge", "nodes_in", "table", "path", "duplicates", "nodes_appended", "elements_appended", "kernels"),
+              5: ("scale", "values", None, None, None, None, None, "kernels"),
+              6: ("product", "values", None, None, None, None, None, "kernels"),
+              7: ("select", "values", None, None, None, None, None, "kernels")}
+    PATHS = ("append", "grid", "brute")
 
     def __init__(self, ctx: Context, nodes, elts):
         self.ctx = ctx
@@ -1553,8 +1562,48 @@ class Surf:
         self.ctx.check(self.ctx.lib.pa_surf_area(self.ctx.h, self.h, C.byref(t), C.byref(lo), C.byref(hi)))
         return t.value, lo.value, hi.value
 
+    @classmethod
+    def _adopt(cls, ctx: Context, handle):
+        if not handle:
+            raise PaError(ctx.lib.pa_last_error(ctx.h).decode())
+        s = cls.__new__(cls)
+        s.ctx, s.h = ctx, handle
+        s.nverts = s.nsegs = 0
+        return s
+
+    def merge(self, other: "Surf", eps: float = 1.0e-8, rem_dup_nodes: bool = False, method: int = 0) -> bool:
+        """mergeMEF.cpp merge_iso: `other` into this surface; method 0 auto, 1 grid, 2 brute force; -> whether anything was appended"""
+        app = C.c_int(0)
+        self.ctx.check(self.ctx.lib.pa_surfjoin_merge(self.ctx.h, self.h, other.h, float(eps), int(bool(rem_dup_nodes)), int(method), C.byref(app)))
+        self.nverts = self.nsegs = 0
+        return bool(app.value)
+
+    def scale(self, comps, vals) -> None:
+        """scaleMEF.cpp: value[comps[k]] *= vals[k], in list order"""
+        if len(comps) != len(vals):
+            raise PaError("Surf.scale: vals needs one value per component")
+        n = len(comps)
+        cc = (C.c_int32 * max(n, 1))(*[int(c) for c in comps])
+        vv = (C.c_double * max(n, 1))(*[float(v) for v in vals])
+        self.ctx.check(self.ctx.lib.pa_surfjoin_scale(self.ctx.h, self.h, n, cc, vv))
+        self.nverts = self.nsegs = 0
+
+    def product(self, comps) -> "Surf":
+        """multMEF.cpp: a new one-component surface, ((1.0 * d[c0]) * d[c1]) * ..."""
+        n = len(comps)
+        cc = (C.c_int32 * max(n, 1))(*[int(c) for c in comps])
+        return Surf._adopt(self.ctx, self.ctx.lib.pa_surfjoin_product(self.ctx.h, self.h, n, cc))
+
+    def select(self, sel, other: Optional["Surf"] = None) -> "Surf":
+        """combineMEF.cpp: a new surface whose columns are sel = [(which, comp) ...], which 0 = this surface, 1 = `other`; this one's elements"""
+        n = len(sel)
+        ww = (C.c_int32 * max(n, 1))(*[int(w) for w, _ in sel])
+        cc = (C.c_int32 * max(n, 1))(*[int(c) for _, c in sel])
+        return Surf._adopt(self.ctx, self.ctx.lib.pa_surfjoin_select(self.ctx.h, self.h, other.h if other is not None else None, n, ww, cc))
+
     def last_launch(self):
-        """{"op": "slice" | "trim" | "area", <item name>: count ...} of the last call"""
+        """{"op": "slice" | "trim" | "area" | "merge" | "scale" | "product" | "select", <item name>: count ...} of the last call; a merge's
+        "path" is one of Surf.PATHS"""
         rec = np.zeros(8, dtype=np.int64)
         self.ctx.check(self.ctx.lib.pa_surf_last_launch(self.h, rec.ctypes.data_as(C.POINTER(C.c_int64))))
         names = self.LAUNCH.get(int(rec[0]))
@@ -1562,6 +1611,8 @@ class Surf:
             return {"op": None}
         out = {"op": names[0]}
         out.update({k: int(v) for k, v in zip(names[1:], rec[1:]) if k})
+        if "path" in out:
+            out["path"] = self.PATHS[out["path"]]
         return out
 
 

@@ -1,5 +1,5 @@
 // pa_surfcut.hip -- cutting and trimming a triangulated surface that stays in device memory (sliceMEF.cpp, trimMEFgen.cpp).
-// A pa_surf holds the nodes COMPONENT-MAJOR, V[c * nN + n] (the classification reads one dense column, the gathers read whole columns),
+// A pa_surf (pa_surf.h: the handle is shared with pa_surfjoin.hip) holds the nodes COMPONENT-MAJOR, V[c * nN + n] (the classification reads one dense column, the gathers read whole columns),
 // and the elements as 0-based int triples F[3 * e + q].
 //   slice   1. case     bit q of case[e] = V[comp][node q of e] < val (strict); a flag where the case is not 0 or 7
 //           2. scan     exclusive scan of the flags: segment s of element e, in element order
@@ -19,12 +19,9 @@
 // Every floating-point value is computed by ONE thread in a written order (the file is built with -ffp-contract=off); lane groups and
 // atomics combine only flags, integer minima / maxima and fixed-point limbs.  The same input gives the same bytes: those of
 // tests/surfcut_ref.py.
-#include <algorithm>
 #include <cfloat>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include "pa_fixed192.h"
-#include "pa_internal.h"
+#include "pa_surf.h"
 
 namespace {
 constexpr double SC_EPS = 1.0e-8;  // epsilon_DEF of sliceMEF.cpp
@@ -33,12 +30,6 @@ enum { SC_LT = 0, SC_LE = 1, SC_GT = 2, SC_GE = 3, SC_EQ = 4 };
 
 __device__ __forceinline__ bool sc_holds(double d, int op, double v) {
   return ((op == SC_LT) & (d < v)) | ((op == SC_LE) & (d <= v)) | ((op == SC_GT) & (d > v)) | ((op == SC_GE) & (d >= v)) | ((op == SC_EQ) & (d == v));
-}
-// the item of this thread in a one-thread-per-item launch.  Counts go up to 2^31 - 1, so the last block's index can pass INT_MAX: it is
-// formed in 64 bits and clamped to INT_MAX, which no count is below, so the callers' `>= n` guards hold it off
-__device__ __forceinline__ int sc_item() {
-  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  return t > 0x7fffffffLL ? 0x7fffffff : (int)t;
 }
 
 // ---------------------------------------------------------------- slice
@@ -220,86 +211,11 @@ __global__ __launch_bounds__(256) void k_sf_elts_out(long long n, const int* F, 
   if (t < n) out[t] = F[t] + 1;
 }
 
-inline dim3 sc_grid(long long n) { return dim3((unsigned)((n + 255) / 256)); }
-
-struct DevBufG {  // grow-only device scratch
-  void* p = nullptr;
-  size_t cap = 0;
-};
-}  // namespace
-
-struct pa_surf {
-  pa_ctx* ctx = nullptr;
-  long long nN = 0, nE = 0;
-  int nc = 0;
-  double* V = nullptr;
-  int* F = nullptr;
-  // the last slice (device memory, valid until the next slice or trim)
-  bool sliced = false;
-  long long nsegs = 0, nverts = 0;
-  int64_t rec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  enum { B_CS, B_FLAG, B_POS, B_SRC, B_UKEY, B_DKEY, B_RIDX, B_UKS, B_RS, B_HEAD, B_HSCAN, B_REQU, B_HSTART, B_VDK, B_VU, B_VDKS, B_PERM, B_RANK, B_LEN, B_OFF,
-         B_SEGS, B_ADJ, B_OFFOUT, B_PAIRS, B_VERTS, B_TMP, B_AUX, B_N };
-  DevBufG buf[B_N];
-};
-
-namespace {
-int sf_fail(pa_ctx* ctx, const std::string& m) { if (ctx) ctx->err = m; return -1; }
-#define SF_HIP(call)                                                                                          \
-  do {                                                                                                        \
-    const hipError_t e_ = (call);                                                                             \
-    if (e_ != hipSuccess) return sf_fail(S->ctx, std::string("pa_surf: " #call ": ") + hipGetErrorString(e_)); \
-  } while (0)
-#define SF_LAUNCH(kernel, n, ...)                                                               \
-  do {                                                                                          \
-    if ((n) > 0) { hipLaunchKernelGGL(kernel, sc_grid((n)), dim3(256), 0, st, __VA_ARGS__); ++launches; } \
-  } while (0)
-
-template <class T> int sf_need(pa_surf* S, int which, size_t n, T*& out) {
-  DevBufG& b = S->buf[which];
-  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-  if (bytes > b.cap) {
-    if (b.p) SF_HIP(hipFree(b.p));
-    b.p = nullptr; b.cap = 0;
-    SF_HIP(hipMalloc(&b.p, bytes));
-    b.cap = bytes;
-  }
-  out = (T*)b.p;
-  return 0;
-}
-int sf_scan(pa_surf* S, const int* in, int* out, size_t n) {
-  size_t tb = 0;
-  SF_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, 0, n, rocprim::plus<int>(), S->ctx->stream));
-  unsigned char* tmp = nullptr;
-  if (sf_need(S, pa_surf::B_TMP, tb + 256, tmp)) return -1;
-  SF_HIP(rocprim::exclusive_scan(tmp, tb, in, out, 0, n, rocprim::plus<int>(), S->ctx->stream));
-  return 0;
-}
-int sf_sort_pairs(pa_surf* S, const u64* kin, u64* kout, const int* vin, int* vout, size_t n, int end_bit) {
-  size_t tb = 0;
-  SF_HIP(rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, n, 0, end_bit, S->ctx->stream));
-  unsigned char* tmp = nullptr;
-  if (sf_need(S, pa_surf::B_TMP, tb + 256, tmp)) return -1;
-  SF_HIP(rocprim::radix_sort_pairs(tmp, tb, kin, kout, vin, vout, n, 0, end_bit, S->ctx->stream));
-  return 0;
-}
-// the total of an exclusive scan of 0 / 1 flags: scan[n - 1] + flag[n - 1]
-int sf_total(pa_surf* S, const int* flag, const int* scan, long long n, long long* tot) {
-  *tot = 0;
-  if (n <= 0) return 0;
-  int last[2];
-  SF_HIP(hipMemcpyAsync(&last[0], scan + (n - 1), sizeof(int), hipMemcpyDeviceToHost, S->ctx->stream));
-  SF_HIP(hipMemcpyAsync(&last[1], flag + (n - 1), sizeof(int), hipMemcpyDeviceToHost, S->ctx->stream));
-  SF_HIP(hipStreamSynchronize(S->ctx->stream));
-  *tot = (long long)last[0] + last[1];
-  return 0;
-}
 int sf_key_bits(long long nN) {  // the directed and unordered keys hold node ids below nN in both halves
   int b = 1;
   while (b < 32 && (1LL << b) < nN) ++b;
   return 32 + b;
 }
-bool sf_own(pa_ctx* ctx, const pa_surf* S) { return ctx && S && S->ctx == ctx; }
 }  // namespace
 
 extern "C" void pa_surf_destroy(pa_surf* S) {
@@ -481,6 +397,7 @@ extern "C" int pa_surf_trim(pa_ctx* ctx, pa_surf* S, int ncond, const int32_t* c
     if (ops[i] < SC_LT || ops[i] > SC_EQ) return pa_fail(ctx, "pa_surf_trim: Bad signs data. Use one of [lt,le,gt,ge,eq]");
   }
   const int use_rxy = rxy >= 0 ? 1 : 0;
+  if (use_rxy && S->nc < 3) return pa_fail(ctx, "pa_surf_trim: RXY needs the node coordinates x, y, z as the first three components, the surface has " + std::to_string(S->nc));
   if (use_rxy && (rxy_op < SC_LT || rxy_op > SC_EQ)) return pa_fail(ctx, "pa_surf_trim: Bad sign data.  Use one of [lt,le,gt,ge,eq]");
   hipStream_t st = ctx->stream;
   int launches = 0;
@@ -535,6 +452,7 @@ extern "C" int pa_surf_trim(pa_ctx* ctx, pa_surf* S, int ncond, const int32_t* c
 extern "C" int pa_surf_area(pa_ctx* ctx, pa_surf* S, double* total, double* amin, double* amax) {  // not const: scratch and the launch record
   PaBind bind_(ctx);
   if (!sf_own(ctx, S)) return pa_fail(ctx, "pa_surf_area: null argument, or the object belongs to another context");
+  if (S->nc < 3) return pa_fail(ctx, "pa_surf_area: needs the node coordinates x, y, z as the first three components, the surface has " + std::to_string(S->nc));
   hipStream_t st = ctx->stream;
   int launches = 0;
   const int nE = (int)S->nE;
