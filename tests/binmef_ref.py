@@ -1,7 +1,9 @@
 """Restatement of the reference's Src/binMEF.cpp in plain Python floats: the area-weighted (joint) PDF of node fields over a triangulated
 surface.  Every triangle is clipped recursively against the bin edges of each binned component; the pieces (leaves) add their area to
-the bin they lie in.  The reference needs AMReX and cannot be compiled here, so there is no golden file: tests/test_binmef_ref.py pins
-this file with known answers, tests/test_gpu_binmef.py pins the kernels (peleanalysis_amd/csrc/pa_binmef.hip) with this file.
+the bin they lie in.  The tool as a program needs AMReX; its arithmetic (triangleArea through processTriangle) does not: `make -C oracle
+ref` compiles it, tests/golden/binmef_ref.npz holds what it returns, and tests/test_surf_reference_pin.py holds this file to that record
+leaf by leaf (tests/test_gpu_surf_reference.py: the kernels).  tests/test_binmef_ref.py pins this file with known answers,
+tests/test_gpu_binmef.py pins the kernels (peleanalysis_amd/csrc/pa_binmef.hip) with this file.
 
 A vertex is the tuple of ALL node components (x, y, z first); a bin vector is a tuple of one index per binned component.  The
 recursion of processTriangle is unrolled onto an explicit stack that visits the calls in the reference's order.

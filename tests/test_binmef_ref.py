@@ -1,5 +1,6 @@
-"""CPU tier: the restatement of binMEF.cpp (tests/binmef_ref.py) against known answers -- the reference needs AMReX and cannot be built
-here, so there is no golden file -- and the C ABI of the surface PDFs (pa_surfbin_*): declared in the header, exported by the library.
+"""CPU tier: the restatement of binMEF.cpp (tests/binmef_ref.py) against known answers -- the comparison with the reference's compiled
+arithmetic and its golden file is tests/test_surf_reference_pin.py -- and the C ABI of the surface PDFs (pa_surfbin_*): declared in the
+header, exported by the library.
 The pure-host entry pa_surfbin_max_area is compared with the restatement's triangle areas."""
 import collections
 import ctypes as C
