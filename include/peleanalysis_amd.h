@@ -729,6 +729,48 @@ int pa_tube_smooth(pa_ctx*, pa_tube*, const double* vals, const double* area, in
 /* the neighbour lists as CSR, to the host: *nnz always; rowptr [nElts + 1] and cols [*nnz] where not NULL (tests) */
 int pa_tube_neighbors(pa_ctx*, pa_tube*, int64_t* nnz, int64_t* rowptr, int32_t* cols);
 
+/* ------------------------------------------------------------- selecting streamlines (streamScatter.cpp, stream2plt.cpp)
+ * DATA LAYOUT and tables: those of the stream tubes above -- box_desc host [nbt][4] = (ni, nj, jlo, off_g), node_table host [nNodes][2] =
+ * (box g, line i) of node id n + 1 (box -1: no box lists the id -- refused), data buffers flat, component-major, i fastest, then j.
+ * The dense array of stream2plt ("final", finalMF of stream2plt.cpp:498-502) is device [component][point][line], line fastest.
+ * NUMERICS: a thread owns a line from its first point to its last; every expression keeps the reference's association, every sum
+ * its order in j, every comparison its literal form (>, <, std::max, std::min: NaN goes the serial code's way); no floating-point
+ * atomics.  The results are the serial code's bits.  All calls are synchronous; arrays are device memory unless called "host".
+ * Boxes, lines and components out of range fail on the host, before any launch, with pa_last_error set. */
+typedef struct pa_ssel pa_ssel;
+pa_ssel* pa_ssel_create(pa_ctx*, int32_t nbt, const int64_t* box_desc, int64_t nNodes, const int32_t* node_table);
+void pa_ssel_destroy(pa_ssel*);
+/* streamScatter.cpp:129-143: along every node's line, over its box's own j range lo .. hi, the peak of component comp of data (ncomp
+ * components): the scan starts at ptOnStr = (int)(0.5 * (lo + hi)) -- truncated toward zero -- with the value there, runs j = lo .. hi
+ * ascending and replaces on strict >.  jpeak, hival [nNodes], by node id. */
+int pa_ssel_peaks(pa_ctx*, pa_ssel*, const double* data, int32_t ncomp, int32_t comp, int32_t* jpeak, double* hival);
+/* streamScatter.cpp:145-154: the nodes with hival >= moreThan && hival < lessThan, compacted in node-id order (an integer scan, no
+ * atomic counter); components comps (host, nvars <= 64) of data at (line, jpeak) go to columns col0 .. col0 + nvars - 1 of the kept
+ * node's row of out [*nkept][stride] -- a caller short of memory passes the variables in groups.  nvars == 0 only counts (jpeak, data
+ * and out may be NULL): size out with it.  *nkept is host. */
+int pa_ssel_scatter(pa_ctx*, pa_ssel*, const double* data, int32_t ncomp, int32_t nvars, const int32_t* comps, const int32_t* jpeak, const double* hival,
+                    double moreThan, double lessThan, int32_t stride, int32_t col0, double* out, int64_t* nkept);
+/* stream2plt.cpp:504-547: the selected lines sel host [nSel][2] = (box g, line i), in level -> box -> line order, as the dense array
+ * final [ncompSel][shi - slo + 1][nSel] of components comps (host) of data.  Every selected box must span exactly j = slo .. shi
+ * (the reference copies that range without a check, :529-540). */
+int pa_ssel_gather_lines(pa_ctx*, pa_ssel*, const double* data, int32_t ncomp, int32_t ncompSel, const int32_t* comps, int64_t nSel, const int32_t* sel,
+                         int32_t slo, int32_t shi, double* final);
+/* one condition of stream2plt.cpp:568-651.  MAX / MIN (:569-600): the running std::max / std::min of selected component comp along the
+ * line, STARTED FROM THE FIRST POINT OF LINE 0 (:574, :591), tested `sgn val`; a failed test clears the line.  RXY (:604-619): the radius
+ * sqrt(c0^2 + c1^2) of selected components 0 and 1 at point (int)(0.5 * (slo + shi)), tested `sgn val`.  AT (:622-651): at the first
+ * segment where comp strictly brackets val2, comp2 interpolated there is tested `sgn val` and the result is ASSIGNED to the line (:646).
+ * sgn: 0 ge, 1 gt, 2 lt, 3 le, 4 eq, 5 ne; any other value is an unknown string and tests false (do_test, :732-751). */
+enum { PA_SSEL_MAX = 0, PA_SSEL_MIN = 1, PA_SSEL_RXY = 2, PA_SSEL_AT = 3 };
+typedef struct { int32_t kind, comp, comp2, sgn; double val, val2; } pa_ssel_cond;
+/* stream2plt.cpp:556-651 in one launch: write_lines [nSel] int32 = 1, then the conditions conds (host) in order -- the kinds must not
+ * descend: max-tests, min-tests, RXY, at-tests, the reference's order.  final holds at least ncompSel components. */
+int pa_ssel_filter(pa_ctx*, const double* final, int32_t ncompSel, int32_t slo, int32_t shi, int64_t nSel, int32_t ncond, const pa_ssel_cond* conds,
+                   int32_t* write_lines);
+/* stream2plt.cpp:654-713: component ncompSel of final [ncompSel + 1][npts][nSel] = the signed arc length: 0 at the first point, the serial
+ * running sum of sqrt(dx^2 + dy^2 + dz^2) over selected components 0 .. 2 after it, minus its value interpolated where distComp first
+ * strictly brackets distVal; without a crossing every point gets 2 * the line's last running sum (:702-709). */
+int pa_ssel_arclength(pa_ctx*, double* final, int32_t ncompSel, int32_t npts, int64_t nSel, int32_t distComp, double distVal);
+
 /* ------------------------------------------------------------ tool pipelines
  * The level loops of the tool mains, operating on device-resident MultiFabs.
  * levels/state/out are arrays of nlev pointers, coarse first. */

@@ -72,6 +72,10 @@ class PaSdfGrid(C.Structure):
                 ("n", C.c_int32 * 3), ("phi", C.c_void_p)]
 
 
+class PaSselCond(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("comp", C.c_int32), ("comp2", C.c_int32), ("sgn", C.c_int32), ("val", C.c_double), ("val2", C.c_double)]
+
+
 _lib = None
 
 
@@ -236,6 +240,13 @@ def load_library() -> C.CDLL:
         "pa_tube_node_avg": (C.c_int, [vp, vp, vp, i32, i32, vp]),
         "pa_tube_smooth": (C.c_int, [vp, vp, vp, vp, i32, vp]),
         "pa_tube_neighbors": (C.c_int, [vp, vp, C.POINTER(i64), C.POINTER(i64), pi32]),
+        "pa_ssel_create": (vp, [vp, i32, C.POINTER(i64), i64, pi32]),
+        "pa_ssel_destroy": (None, [vp]),
+        "pa_ssel_peaks": (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),
+        "pa_ssel_scatter": (C.c_int, [vp, vp, vp, i32, i32, pi32, vp, vp, dbl, dbl, i32, i32, vp, C.POINTER(i64)]),
+        "pa_ssel_gather_lines": (C.c_int, [vp, vp, vp, i32, i32, pi32, i64, pi32, i32, i32, vp]),
+        "pa_ssel_filter": (C.c_int, [vp, vp, i32, i32, i32, i64, i32, C.POINTER(PaSselCond), vp]),
+        "pa_ssel_arclength": (C.c_int, [vp, vp, i32, i32, i64, i32, dbl]),
         "pa_smooth_last": (C.c_int, [vp, C.POINTER(C.c_int), pdbl]),
         "pa_curvature_last_path": (C.c_int, [vp]),
         "pa_level_free_scratch": (i64, [vp]),
@@ -968,6 +979,99 @@ class Tube:
     def close(self):
         if self.h:
             self.ctx.lib.pa_tube_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.ctx.h:
+                self.close()
+        except Exception:
+            pass
+
+
+SSEL_MAX, SSEL_MIN, SSEL_RXY, SSEL_AT = 0, 1, 2, 3
+SSEL_SIGNS = {"ge": 0, "gt": 1, "lt": 2, "le": 3, "eq": 4, "ne": 5}  # do_test (stream2plt.cpp:732-751); any other string tests false (-1)
+
+
+class StreamSel:
+    """pa_ssel (streamScatter.cpp, stream2plt.cpp): the tables of one stream directory -- box_desc and node_table as for Tube -- and
+    the selection calls on them.  data arguments: flat buffers in the layout of Tube.flat, host arrays (uploaded) or DevBufs."""
+
+    def __init__(self, ctx: Context, box_desc, node_table=(), out_fill=None, int_fill=None):
+        """out_fill / int_fill: the uint64 / int32 bit pattern every output double / int starts from (tests: a sentinel no call may
+        leave behind); None: whatever the allocation holds (zeros for the dense array of gather_lines)"""
+        self.ctx, self.out_fill, self.int_fill = ctx, out_fill, int_fill
+        self.box = np.ascontiguousarray(box_desc, dtype=np.int64).reshape(-1, 4)
+        self.node = np.ascontiguousarray(node_table, dtype=np.int32).reshape(-1, 2)
+        self.nNodes = len(self.node)
+        self.h = ctx.lib.pa_ssel_create(ctx.h, len(self.box), self.box.ctypes.data_as(C.POINTER(C.c_int64)), self.nNodes,
+                                        self.node.ctypes.data_as(C.POINTER(C.c_int32)))
+        if not self.h:
+            raise PaError(ctx.lib.pa_last_error(ctx.h).decode())
+
+    def _f64(self, n) -> "DevBuf":
+        n = max(1, int(n))
+        return DevBuf(self.ctx, 8 * n) if self.out_fill is None else DevBuf.from_numpy(self.ctx, np.full(n, self.out_fill, dtype=np.uint64))
+
+    def _i32(self, n) -> "DevBuf":
+        n = max(2, int(n))
+        return DevBuf(self.ctx, 4 * n) if self.int_fill is None else DevBuf.from_numpy(self.ctx, np.full(n, self.int_fill, dtype=np.int32))
+
+    def peaks(self, data, ncomp: int, comp: int, on_device: bool = False):
+        """pa_ssel_peaks -> (jpeak [nNodes] int32, hival [nNodes]); on_device: the two DevBufs"""
+        N = self.nNodes
+        d, j, h = _dev(self.ctx, data), self._i32(N), self._f64(N)
+        self.ctx.check(self.ctx.lib.pa_ssel_peaks(self.ctx.h, self.h, d.ptr, int(ncomp), int(comp), j.ptr, h.ptr))
+        return (j, h) if on_device else (j.to_numpy(np.int32, (N,)), h.to_numpy(np.float64, (N,)))
+
+    def scatter(self, data, ncomp: int, comps, jpeak, hival, more_than: float, less_than: float, group: Optional[int] = None) -> np.ndarray:
+        """pa_ssel_scatter -> [nkept][len(comps)], the kept nodes in node-id order; group: variables per call (the same rows)"""
+        comps = np.ascontiguousarray(comps, dtype=np.int32)
+        d = _dev(self.ctx, data)
+        j = jpeak if isinstance(jpeak, DevBuf) else _dev(self.ctx, np.asarray(jpeak, np.int32))
+        h = hival if isinstance(hival, DevBuf) else _dev(self.ctx, np.asarray(hival, np.float64))
+        n = C.c_int64(-1)
+        self.ctx.check(self.ctx.lib.pa_ssel_scatter(self.ctx.h, self.h, None, int(ncomp), 0, None, None, h.ptr, float(more_than), float(less_than), 0, 0, None,
+                                                    C.byref(n)))
+        nv = len(comps)
+        out = self._f64(n.value * nv)
+        group = group or 64
+        for c0 in range(0, nv, group):
+            part, m = comps[c0:c0 + group], C.c_int64(-1)
+            self.ctx.check(self.ctx.lib.pa_ssel_scatter(self.ctx.h, self.h, d.ptr, int(ncomp), len(part), part.ctypes.data_as(C.POINTER(C.c_int32)), j.ptr, h.ptr,
+                                                        float(more_than), float(less_than), nv, c0, out.ptr, C.byref(m)))
+            assert m.value == n.value
+        return out.to_numpy(np.float64, (n.value, nv))
+
+    def gather_lines(self, data, ncomp: int, comps, sel, slo: int, shi: int, extra: int = 0, on_device: bool = False):
+        """pa_ssel_gather_lines -> final [len(comps) + extra][shi - slo + 1][nSel]; the extra components are zero (out_fill: the whole array starts as the pattern)"""
+        comps = np.ascontiguousarray(comps, dtype=np.int32)
+        sel = np.ascontiguousarray(sel, dtype=np.int32).reshape(-1, 2)
+        shape = (len(comps) + extra, shi - slo + 1, len(sel))
+        d, f = _dev(self.ctx, data), (self._f64(np.prod(shape)) if self.out_fill is not None else DevBuf.from_numpy(self.ctx, np.zeros(max(1, int(np.prod(shape))))))
+        self.ctx.check(self.ctx.lib.pa_ssel_gather_lines(self.ctx.h, self.h, d.ptr, int(ncomp), len(comps), comps.ctypes.data_as(C.POINTER(C.c_int32)), len(sel),
+                                                         sel.ctypes.data_as(C.POINTER(C.c_int32)), int(slo), int(shi), f.ptr))
+        return f if on_device else f.to_numpy(np.float64, shape)
+
+    def filter(self, final, ncompSel: int, slo: int, shi: int, nSel: int, conds) -> np.ndarray:
+        """pa_ssel_filter -> write_lines [nSel] int32.  conds: (kind, comp, comp2, sgn string or code, val, val2)"""
+        arr = (PaSselCond * max(1, len(conds)))()
+        for q, (kind, comp, comp2, sgn, val, val2) in zip(arr, conds):
+            q.kind, q.comp, q.comp2, q.val, q.val2 = int(kind), int(comp), int(comp2), float(val), float(val2)
+            q.sgn = SSEL_SIGNS.get(sgn, -1) if isinstance(sgn, str) else int(sgn)
+        f, w = _dev(self.ctx, final), self._i32(nSel)
+        self.ctx.check(self.ctx.lib.pa_ssel_filter(self.ctx.h, f.ptr, int(ncompSel), int(slo), int(shi), int(nSel), len(conds), arr, w.ptr))
+        return w.to_numpy(np.int32, (nSel,))
+
+    def arclength(self, final, ncompSel: int, npts: int, nSel: int, distComp: int, distVal: float) -> np.ndarray:
+        """pa_ssel_arclength on final [ncompSel + 1][npts][nSel] (a host array is uploaded) -> the array with component ncompSel filled"""
+        f = _dev(self.ctx, final)
+        self.ctx.check(self.ctx.lib.pa_ssel_arclength(self.ctx.h, f.ptr, int(ncompSel), int(npts), int(nSel), int(distComp), float(distVal)))
+        return f.to_numpy(np.float64, (ncompSel + 1, npts, nSel))
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.pa_ssel_destroy(self.h)
             self.h = None
 
     def __del__(self):

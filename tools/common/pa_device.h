@@ -1,5 +1,6 @@
 // pa_device.h -- glue between the host plotfile containers and the C ABI (device levels / multifabs)
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <future>
 #include <memory>
@@ -18,6 +19,21 @@ struct Ctx {
   void check(int rc) const {
     if (rc != 0) Abort(pa_last_error(h));
   }
+};
+
+// raw device memory of the library's context (pa_device_malloc), freed with the object; up / down are synchronous copies
+struct DBuf {
+  const Ctx& c;
+  void* p = nullptr;
+  DBuf(const Ctx& ctx, size_t bytes) : c(ctx) {
+    p = pa_device_malloc(c.h, (int64_t)std::max<size_t>(bytes, 8));
+    if (!p) Abort(pa_last_error(c.h));
+  }
+  ~DBuf() { pa_device_free(c.h, p); }
+  DBuf(const DBuf&) = delete;
+  double* d() const { return (double*)p; }
+  void up(const void* h, size_t bytes) const { if (bytes) c.check(pa_memcpy_h2d(c.h, p, h, (int64_t)bytes)); }
+  void down(void* h, size_t bytes) const { if (bytes) c.check(pa_memcpy_d2h(c.h, h, p, (int64_t)bytes)); }
 };
 
 // HIP context brought up on a second thread (~0.25 s of runtime start-up) while the caller reads the plotfile

@@ -15,21 +15,9 @@
 // grad_use_eps and nCompsPerPass are keys of our own (nCompsPerPass bounds memory only).
 #include "../common/pa_device.h"
 
-namespace {
+using pa::DBuf;
 
-struct DBuf {  // device memory of the library's context
-  const pa::Ctx& c;
-  void* p = nullptr;
-  DBuf(const pa::Ctx& ctx, size_t bytes) : c(ctx) {
-    p = pa_device_malloc(c.h, (int64_t)std::max<size_t>(bytes, 8));
-    if (!p) pa::Abort(pa_last_error(c.h));
-  }
-  ~DBuf() { pa_device_free(c.h, p); }
-  DBuf(const DBuf&) = delete;
-  double* d() const { return (double*)p; }
-  void up(const void* h, size_t bytes) const { if (bytes) c.check(pa_memcpy_h2d(c.h, p, h, (int64_t)bytes)); }
-  void down(void* h, size_t bytes) const { if (bytes) c.check(pa_memcpy_d2h(c.h, h, p, (int64_t)bytes)); }
-};
+namespace {
 
 // :314-317 (Tokenize skips empty tokens) where the directory part has no '.'; otherwise only a final .ext of the last path component goes
 std::string out_root(const std::string& infile) {
