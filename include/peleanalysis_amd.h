@@ -1029,7 +1029,9 @@ int pa_surf_area(pa_ctx*, pa_surf*, double* total, double* amin, double* amax);
  * area: [1] elements, [2] terms added in fixed point.
  * rec[0] = 4 merge / 5 scale / 6 product / 7 select (below).  merge: [1] nodes of S, [2] nodes of M entered in the table (0 off the grid
  * path), [3] path taken: 0 append, 1 grid, 2 brute force, [4] duplicates found, [5] nodes appended, [6] elements appended;
- * scale, product, select: [1] values written. */
+ * scale, product, select: [1] values written.
+ * rec[0] = 8 smooth (below): [1] elements, [2] incidence entries sorted (3 * nelts), [3] neighbour entries (the sum of |N(e)|),
+ * [4] iterations run, [5] nodes written, [6] the largest |N(e)|, [7] kernels launched (scans and sorts not counted, as for every op). */
 int pa_surf_last_launch(const pa_surf*, int64_t rec[8]);
 void pa_surf_destroy(pa_surf*);
 
@@ -1067,6 +1069,35 @@ pa_surf* pa_surfjoin_product(pa_ctx*, const pa_surf*, int n, const int32_t* comp
  * intersection of the two boxes and leaves the rest uninitialised -- where the node counts differ.  The launch record is the NEW
  * handle's; L and R are not touched. */
 pa_surf* pa_surfjoin_select(pa_ctx*, const pa_surf* L, const pa_surf* R_or_null, int nsel, const int32_t* which, const int32_t* comps);
+
+/* ------------------------------------------------------------- smoothing a node field over a surface (smoothMEF.cpp)
+ * The same handle: merge -> smooth -> trim -> slice runs without leaving the device.  NUMERICS as above; the bytes are
+ * those of the restatement tests/surfsmooth_ref.py.  The two entries are named after their file (pa_surfsmooth.hip), as the
+ * pa_surfjoin_* ones are; they take the pa_surf handle of pa_surf_create. */
+/* smoothMEF.cpp:224-273 as it is evidently meant, with d = component comp and (n0, n1, n2) the nodes of element e in file order:
+ *   weights   0 <= area_comp < ncomp: w_e = ((A[n0] + A[n1]) + A[n2]) * (1./3) with A that component (:249-256); otherwise w_e = the area of
+ *             triangle e by the written expression of triangle_area (:160-194): R1 = pb - pa, R2 = pc - pa, R3 = R1 x R2 as written there,
+ *             res = ((0 + R3x*R3x) + R3y*R3y) + R3z*R3z, 0.5 * sqrt(res).  The coordinates are read before anything is written, so
+ *             comp < 3 (smoothing a coordinate) is well defined
+ *   values    q_e = ((d[n0] + d[n1]) + d[n2]) * (1./3)
+ *   N(e)      buildNodeNeighbors (:94-131): the elements other than e that share at least one node with e, each once, ascending
+ *   iterate   W_e = w_e + sum of w_nb, nb ascending, added one by one; each of the nsmooth Jacobi iterations sets
+ *             q'_e = ((w_e*q_e) + sum of (w_nb*q_nb)) / W_e in the same order from the previous iteration's q only (smoothVals, :134-157);
+ *             where !(W_e > 0), q'_e = q_e
+ *   nodes     node n with incident elements E(n), ascending, each once: Wn = sum of w_e, Sn = sum of (w_e*q_e), d[n] = Sn / Wn where
+ *             Wn > 0; a node with !(Wn > 0), or one that no element uses, keeps its value.  No other component is touched.
+ *             nsmooth = 0 still averages to the elements and back.
+ * Deviations from the letter of smoothMEF.cpp, whose output is meaningless or undefined: without areaComp it indexes an array of
+ * element areas by node id (:241-242, :252); it weights each node value by the running partial area sum (:253), feeds the intensive
+ * result of smoothVals back in as value * area (:155, :267-269) and divides by the area once more (:273); and it writes the nElts
+ * element values over the first nElts slots of the nNodes node values (:272-273), a heap overrun for nElts > nNodes.
+ * In place; a slice the handle held is dropped.  Refused, with the handle left as it was (nodes, elements, slice, launch record):
+ * comp out of range, nsmooth < 0, fewer than three components when area_comp is out of range, a sum of |N(e)| beyond 2^31 - 1. */
+int pa_surfsmooth_run(pa_ctx*, pa_surf*, int comp, int area_comp, int nsmooth);
+/* the last smooth of this handle: the neighbour lists as a CSR (nbr_off [nelts + 1], nbr_adj [nbr_off[nelts]], element ids 0-based),
+ * w [nelts], and q [nelts] after the last iteration; valid until the next operation on the handle.  Any pointer may be NULL.  The
+ * sizes are those of the launch record: nelts = rec[1], nbr_off[nelts] = rec[3].  Fails where the handle has not been smoothed. */
+int pa_surfsmooth_read(pa_ctx*, const pa_surf*, int32_t* nbr_off, int32_t* nbr_adj, double* w, double* q);
 
 #ifdef __cplusplus
 }

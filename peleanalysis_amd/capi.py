@@ -292,6 +292,8 @@ def load_library() -> C.CDLL:
         "pa_surfjoin_scale": (C.c_int, [vp, vp, C.c_int, pi32, pdbl]),
         "pa_surfjoin_product": (vp, [vp, vp, C.c_int, pi32]),
         "pa_surfjoin_select": (vp, [vp, vp, vp, C.c_int, pi32, pi32]),
+        "pa_surfsmooth_run": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int]),
+        "pa_surfsmooth_read": (C.c_int, [vp, vp, pi32, pi32, pdbl, pdbl]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -1588,7 +1590,8 @@ class Surf:
               4: ("merge", "nodes_in", "table", "path", "duplicates", "nodes_appended", "elements_appended", "kernels"),
               5: ("scale", "values", None, None, None, None, None, "kernels"),
               6: ("product", "values", None, None, None, None, None, "kernels"),
-              7: ("select", "values", None, None, None, None, None, "kernels")}
+              7: ("select", "values", None, None, None, None, None, "kernels"),
+              8: ("smooth", "elements", "incidence", "neighbours", "iterations", "nodes_written", "max_neighbours", "kernels")}
     PATHS = ("append", "grid", "brute")
 
     def __init__(self, ctx: Context, nodes, elts):
@@ -1705,8 +1708,26 @@ class Surf:
         cc = (C.c_int32 * max(n, 1))(*[int(c) for _, c in sel])
         return Surf._adopt(self.ctx, self.ctx.lib.pa_surfjoin_select(self.ctx.h, self.h, other.h if other is not None else None, n, ww, cc))
 
+    def smooth(self, comp: int, area_comp: int = -1, nsmooth: int = 1) -> None:
+        """smoothMEF.cpp: component comp to the elements, nsmooth area-weighted Jacobi averages over each element and the elements that
+        share a node with it, and back to the nodes; the weights are component area_comp where it names one, else the triangles' areas"""
+        self.ctx.check(self.ctx.lib.pa_surfsmooth_run(self.ctx.h, self.h, int(comp), int(area_comp), int(nsmooth)))
+        self.nverts = self.nsegs = 0
+
+    def smooth_read(self, fill=None):
+        """the last smooth: (nbr_off [nelts + 1], nbr_adj, w [nelts], q [nelts] after the last iteration); element ids 0-based"""
+        rec = self.last_launch()
+        if rec["op"] != "smooth":
+            raise PaError("Surf.smooth_read: the last operation on the surface was not a smooth")
+        ne, na = rec["elements"], rec["neighbours"]
+        o = _out_array
+        off, adj, w, q = o((ne + 1,), np.int32, fill), o((na,), np.int32, fill), o((ne,), np.float64, fill), o((ne,), np.float64, fill)
+        p32, pd = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self.ctx.check(self.ctx.lib.pa_surfsmooth_read(self.ctx.h, self.h, off.ctypes.data_as(p32), adj.ctypes.data_as(p32), w.ctypes.data_as(pd), q.ctypes.data_as(pd)))
+        return off, adj, w, q
+
     def last_launch(self):
-        """{"op": "slice" | "trim" | "area" | "merge" | "scale" | "product" | "select", <item name>: count ...} of the last call; a merge's
+        """{"op": "slice" | "trim" | "area" | "merge" | "scale" | "product" | "select" | "smooth", <item name>: count ...} of the last call; a merge's
         "path" is one of Surf.PATHS"""
         rec = np.zeros(8, dtype=np.int64)
         self.ctx.check(self.ctx.lib.pa_surf_last_launch(self.h, rec.ctypes.data_as(C.POINTER(C.c_int64))))

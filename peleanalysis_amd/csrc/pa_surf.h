@@ -1,6 +1,6 @@
-// pa_surf.h -- the surface handle that pa_surfcut.hip (slice, trim, area) and pa_surfjoin.hip (merge, scale, product, select) share:
-// struct pa_surf and the helpers that size its scratch, scan, sort and launch.  A pa_surf holds the nodes COMPONENT-MAJOR,
-// V[c * nN + n], and the elements as 0-based int triples F[3 * e + q].
+// pa_surf.h -- the surface handle that pa_surfcut.hip (slice, trim, area), pa_surfjoin.hip (merge, scale, product, select) and
+// pa_surfsmooth.hip (smooth) share: struct pa_surf and the helpers that size its scratch, scan, sort and launch.  A pa_surf holds the
+// nodes COMPONENT-MAJOR, V[c * nN + n], and the elements as 0-based int triples F[3 * e + q].
 #pragma once
 #include <algorithm>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -20,12 +20,15 @@ struct pa_surf {
   int nc = 0;
   double* V = nullptr;
   int* F = nullptr;
-  // the last slice (device memory, valid until the next slice, trim, merge or scale)
+  // the last slice (device memory, valid until the next slice, trim, merge, scale or smooth)
   bool sliced = false;
   long long nsegs = 0, nverts = 0;
   int64_t rec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   enum { B_CS, B_FLAG, B_POS, B_SRC, B_UKEY, B_DKEY, B_RIDX, B_UKS, B_RS, B_HEAD, B_HSCAN, B_REQU, B_HSTART, B_VDK, B_VU, B_VDKS, B_PERM, B_RANK, B_LEN, B_OFF,
-         B_SEGS, B_ADJ, B_OFFOUT, B_PAIRS, B_VERTS, B_TMP, B_AUX, B_N };
+         B_SEGS, B_ADJ, B_OFFOUT, B_PAIRS, B_VERTS, B_TMP, B_AUX,
+         B_SM_OFF, B_SM_ADJ, B_SM_W, B_SM_WSUM, B_SM_Q0, B_SM_Q1,  // the last smooth (pa_surfsmooth.hip): no other step writes these
+         B_N };
+  int sm_q = 0;  // which of B_SM_Q0 / B_SM_Q1 holds q after the last iteration
   DevBufG buf[B_N];
 };
 
