@@ -771,6 +771,52 @@ int pa_ssel_filter(pa_ctx*, const double* final, int32_t ncompSel, int32_t slo, 
  * strictly brackets distVal; without a crossing every point gets 2 * the line's last running sum (:702-709). */
 int pa_ssel_arclength(pa_ctx*, double* final, int32_t ncompSel, int32_t npts, int64_t nSel, int32_t distComp, double distVal);
 
+/* ------------------------------------------------------------- subsetting a stream directory by elements (streamSub.cpp)
+ * The streamlines of a few surface elements cut out of a stream directory: the selected connectivity, the Str boxes it needs -- kept
+ * WHOLE, in the file's order --, new consecutive node numbers over them, and their data copied to a compact buffer.
+ * DATA LAYOUT and tables: those of pa_ssel above (box_desc, node_table, flat buffers: box g at ncomp * off_g doubles, component-major,
+ * i fastest, then j).  face: device int32 [nElts][npe], 1-based node ids, npe >= 1.  The compact buffer has the same layout over the
+ * kept boxes: kept box b' at ncompOut * off'_b'.
+ * INTENT, NOT TEXT: streamSub.cpp:337-343 writes EVERY selected element over slots 0 .. nodesPerElt-1 of faceData (the last one wins,
+ * the other slots stay zero) and :380-388 then reads that shrunken array at the FILE's element offset, so the reference is defined for
+ * sElt=0 nElt=1 only.  Built here: faceSel[j * npe + i] = fileFace[E[j] * npe + i], and a box is needed iff it lists a node of faceSel.
+ * DETERMINISM: no atomics.  Every count and position comes from an integer scan; boxes are flagged by plain stores of the value 1.
+ * The copy moves 64-bit patterns (NaN payloads survive).  Two runs give the same bytes.  All calls are synchronous.
+ * The handle's tables must put the ids of every box on its lines 0 .. n-1, one id a line (what build_nodeMap, :228-250, produces from
+ * inside_nodes lists no longer than their boxes): checked on the host at the first call, refused with pa_last_error set otherwise. */
+typedef struct pa_ssub pa_ssub;
+/* NEW (Docs/source/streamSub.rst: "by physical location of the streamline seed point"; no line of streamSub.cpp does it): element e is
+ * kept iff for each of its npe nodes the seed point x = components 0, 1, 2 of data (ncomp >= 3 components) at j = 0 of the node's line
+ * has lo[d] <= x[d] && x[d] <= hi[d] for d = 0, 1, 2 -- literal comparisons, a NaN fails.  elts device [nElts] receives the kept
+ * element indices (0-based) ascending: a count per 256 elements, a scan of the counts, a scatter that recomputes the flag.  *nsel (host)
+ * = their number.  A box with lines whose j range lacks 0 is refused on the host; a node id outside 1 .. nNodes in face is found by the
+ * count pass (nothing is read through it), the scatter then stores nothing and the call fails with elts as it was.  launch (host, may be NULL) = elements, count blocks,
+ * passes of the one-workgroup scan over them, kept elements. */
+int pa_ssub_select_seedbox(pa_ctx*, pa_ssel*, const double* data, int32_t ncomp, int64_t nElts, int32_t npe, const int32_t* face, const double lo[3], const double hi[3],
+                           int32_t* elts, int64_t* nsel, int64_t launch[4]);
+/* streamSub.cpp:337-343 (as intended), :375-395, :417-425, :439-441 for the element list elts device [nSel] (0-based file indices, any
+ * order, duplicates repeat the element): gathers faceSel, flags the needed boxes, scans flag / listed lines / points / copy chunks over
+ * the boxes in int64 (one workgroup up to 256 boxes, block sums beyond), numbers the nodes of the kept boxes 1 .. in level -> box ->
+ * position order, maps faceSel through them and builds the chunk table of the copy.  NULL with pa_last_error set when nSel == 0, an
+ * element id lies outside 0 .. nElts-1, face names an id outside 1 .. nNodes (nothing is read through a bad id), or the new node count
+ * does not fit int32.  The plan refers to the pa_ssel: destroy it first. */
+pa_ssub* pa_ssub_plan(pa_ctx*, pa_ssel*, int64_t nElts, int32_t npe, const int32_t* face, int64_t nSel, const int32_t* elts);
+void pa_ssub_destroy(pa_ssub*);
+/* counts host [3] = kept boxes, new nodes (:411-416 `tot`), points of the kept boxes */
+int pa_ssub_counts(const pa_ssub*, int64_t counts[3]);
+/* ReadMF (:267-304) for the kept boxes: components comps (host, ncompSel <= 64 a call) of data (ncomp components) become components
+ * c0 .. c0 + ncompSel - 1 of out (ncompOut components of counts[2] points) -- a caller short of memory passes the components in groups,
+ * holding only a group's in data.  A segmented copy from chunk records (at most 2048 doubles of one (box, component) run each), 16-byte
+ * accesses where source and destination share the alignment, 8-byte ones otherwise.  out must not overlap data. */
+int pa_ssub_gather(pa_ctx*, pa_ssub*, const double* data, int32_t ncomp, int32_t ncompSel, const int32_t* comps, double* out, int32_t ncompOut, int32_t c0);
+/* to the host, each where not NULL: kept [counts[0]] = the old flat index g of every kept box (ascending: the std::set order of :392 within
+ * a level); box_desc [counts[0]][4] = (ni, nj, jlo, off') of the kept boxes; newNum [nNodes] = the new number of node id n + 1 (the map of
+ * :417-425), 0 where its box is not kept; faceSel [nSel][npe] in the new numbers (:439-441) */
+int pa_ssub_read(pa_ctx*, pa_ssub*, int32_t* kept, int64_t* box_desc, int32_t* newNum, int32_t* faceSel);
+/* what the plan launched: rec = nElts, nSel, boxes, kept boxes, copy chunks, box-scan path (1 one workgroup, 2 block sums), box-scan
+ * workgroups, workgroups of the last pa_ssub_gather (chunks * components; 0 before the first) */
+int pa_ssub_last_launch(const pa_ssub*, int64_t rec[8]);
+
 /* ------------------------------------------------------------ tool pipelines
  * The level loops of the tool mains, operating on device-resident MultiFabs.
  * levels/state/out are arrays of nlev pointers, coarse first. */

@@ -247,6 +247,13 @@ def load_library() -> C.CDLL:
         "pa_ssel_gather_lines": (C.c_int, [vp, vp, vp, i32, i32, pi32, i64, pi32, i32, i32, vp]),
         "pa_ssel_filter": (C.c_int, [vp, vp, i32, i32, i32, i64, i32, C.POINTER(PaSselCond), vp]),
         "pa_ssel_arclength": (C.c_int, [vp, vp, i32, i32, i64, i32, dbl]),
+        "pa_ssub_select_seedbox": (C.c_int, [vp, vp, vp, i32, i64, i32, vp, pdbl, pdbl, vp, C.POINTER(i64), C.POINTER(i64)]),
+        "pa_ssub_plan": (vp, [vp, vp, i64, i32, vp, i64, vp]),
+        "pa_ssub_destroy": (None, [vp]),
+        "pa_ssub_counts": (C.c_int, [vp, C.POINTER(i64)]),
+        "pa_ssub_gather": (C.c_int, [vp, vp, vp, i32, i32, pi32, vp, i32, i32]),
+        "pa_ssub_read": (C.c_int, [vp, vp, pi32, C.POINTER(i64), pi32, pi32]),
+        "pa_ssub_last_launch": (C.c_int, [vp, C.POINTER(i64)]),
         "pa_smooth_last": (C.c_int, [vp, C.POINTER(C.c_int), pdbl]),
         "pa_curvature_last_path": (C.c_int, [vp]),
         "pa_level_free_scratch": (i64, [vp]),
@@ -1074,6 +1081,85 @@ class StreamSel:
     def close(self):
         if self.h:
             self.ctx.lib.pa_ssel_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.ctx.h:
+                self.close()
+        except Exception:
+            pass
+
+
+class StreamSub:
+    """pa_ssub (streamSub.cpp): the subset of one stream directory that a list of surface elements needs, on the tables of a StreamSel.
+    face [nElts][npe] 1-based node ids and elts [nSel] 0-based element indices: host arrays (uploaded) or DevBufs.  out_fill / int_fill
+    as for StreamSel: the pattern every output starts from."""
+
+    PATHS = {1: "one_workgroup", 2: "block_sums"}
+
+    def __init__(self, sel: "StreamSel", face, npe: int, elts, nElts: Optional[int] = None, nSel: Optional[int] = None):
+        self.sel, self.ctx, self.npe, self.h = sel, sel.ctx, int(npe), None
+        self.face = face if isinstance(face, DevBuf) else _dev(self.ctx, np.ascontiguousarray(face, dtype=np.int32))
+        self.nElts = int(nElts) if nElts is not None else np.asarray(face).size // self.npe
+        e = elts if isinstance(elts, DevBuf) else _dev(self.ctx, np.ascontiguousarray(elts, dtype=np.int32))
+        self.nSel = int(nSel) if nSel is not None else len(elts)
+        self.h = self.ctx.lib.pa_ssub_plan(self.ctx.h, sel.h, self.nElts, self.npe, self.face.ptr, self.nSel, e.ptr)
+        if not self.h:
+            raise PaError(self.ctx.lib.pa_last_error(self.ctx.h).decode())
+
+    @staticmethod
+    def select_seedbox(sel: "StreamSel", data, ncomp: int, face, npe: int, lo, hi, nElts: Optional[int] = None, on_device: bool = False):
+        """pa_ssub_select_seedbox -> (the kept element indices, ascending; launch = dict(elements, blocks, scan_passes, kept)); on_device: the
+        DevBuf of nElts ints and the count instead of the array"""
+        ctx = sel.ctx
+        f = face if isinstance(face, DevBuf) else _dev(ctx, np.ascontiguousarray(face, dtype=np.int32))
+        nElts = int(nElts) if nElts is not None else np.asarray(face).size // int(npe)
+        d, e = _dev(ctx, data), sel._i32(nElts)
+        n, rec = C.c_int64(-1), np.full(4, -1, np.int64)
+        ctx.check(ctx.lib.pa_ssub_select_seedbox(ctx.h, sel.h, d.ptr, int(ncomp), nElts, int(npe), f.ptr, _d3(lo), _d3(hi), e.ptr, C.byref(n),
+                                                 rec.ctypes.data_as(C.POINTER(C.c_int64))))
+        launch = dict(zip(("elements", "blocks", "scan_passes", "kept"), (int(v) for v in rec)))
+        return ((e, n.value) if on_device else e.to_numpy(np.int32, (max(2, nElts),))[:n.value]), launch
+
+    def counts(self):
+        """pa_ssub_counts -> (kept boxes, new nodes, points of the kept boxes)"""
+        c = np.zeros(3, np.int64)
+        self.ctx.check(self.ctx.lib.pa_ssub_counts(self.h, c.ctypes.data_as(C.POINTER(C.c_int64))))
+        return int(c[0]), int(c[1]), int(c[2])
+
+    def gather(self, data, ncomp: int, comps, group: Optional[int] = None, on_device: bool = False):
+        """pa_ssub_gather -> the compact buffer [len(comps) * points], flat in the layout of Tube.flat over the kept boxes; group: components
+        per call (the same bytes)"""
+        comps = np.ascontiguousarray(comps, dtype=np.int32)
+        d, out = _dev(self.ctx, data), self.sel._f64(len(comps) * self.counts()[2])
+        group = group or 64
+        for c0 in range(0, len(comps), group):
+            part = np.ascontiguousarray(comps[c0:c0 + group])
+            self.ctx.check(self.ctx.lib.pa_ssub_gather(self.ctx.h, self.h, d.ptr, int(ncomp), len(part), part.ctypes.data_as(C.POINTER(C.c_int32)), out.ptr, len(comps), c0))
+        return out if on_device else out.to_numpy(np.float64, (len(comps) * self.counts()[2],))
+
+    def read(self, fill=None):
+        """pa_ssub_read -> dict(kept [boxes] old flat box index, box_desc [boxes][4], newNum [nNodes], faceSel [nSel][npe]); fill: the int
+        every entry starts from"""
+        nb = self.counts()[0]
+        mk = lambda shape, dt: np.full(shape, 0 if fill is None else fill, dtype=dt)
+        kept, box, num, face = mk(nb, np.int32), mk((nb, 4), np.int64), mk(self.sel.nNodes, np.int32), mk((self.nSel, self.npe), np.int32)
+        p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        self.ctx.check(self.ctx.lib.pa_ssub_read(self.ctx.h, self.h, kept.ctypes.data_as(p32), box.ctypes.data_as(p64), num.ctypes.data_as(p32), face.ctypes.data_as(p32)))
+        return dict(kept=kept, box_desc=box, newNum=num, faceSel=face)
+
+    def last_launch(self):
+        """pa_ssub_last_launch as a dict"""
+        rec = np.zeros(8, np.int64)
+        self.ctx.check(self.ctx.lib.pa_ssub_last_launch(self.h, rec.ctypes.data_as(C.POINTER(C.c_int64))))
+        out = dict(zip(("nElts", "nSel", "boxes", "kept_boxes", "chunks", "path", "scan_blocks", "gather_blocks"), (int(v) for v in rec)))
+        out["path"] = self.PATHS.get(out["path"])
+        return out
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.pa_ssub_destroy(self.h)
             self.h = None
 
     def __del__(self):

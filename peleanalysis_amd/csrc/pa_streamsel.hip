@@ -12,22 +12,9 @@
 // NaN goes the way it goes in the serial code.  The results are the serial code's bits for every launch shape.  The only scan is
 // over the integer keep flags: it compacts the kept nodes in node-id order.
 #include "pa_internal.h"
+#include "pa_streamsel.h"
 
 #include <algorithm>
-
-struct pa_ssel {
-  pa_ctx* ctx = nullptr;
-  int nbt = 0;
-  long long nNodes = 0;
-  std::vector<long long> box;  // [nbt][4]: ni, nj, jlo, off (points of the boxes before)
-  std::vector<int> node;       // [nNodes][2]: box, i
-  long long* d_box = nullptr;
-  int* d_node = nullptr;
-  int* d_order = nullptr;      // node ids sorted by (box, i): consecutive threads of the peak kernel read consecutive i of one box
-  int* d_bsum = nullptr;       // kept nodes of every block of SS_BLOCK node ids
-  long long* d_boff = nullptr; // their exclusive scan, [nblocks + 1]
-  int* d_err = nullptr;        // set by a kernel that was handed a j outside its box
-};
 
 namespace {
 
@@ -332,7 +319,7 @@ extern "C" pa_ssel* pa_ssel_create(pa_ctx* ctx, int32_t nbt, const int64_t* box_
 extern "C" void pa_ssel_destroy(pa_ssel* s) {
   if (!s) return;
   PaBind bind_(s->ctx);
-  for (void* p : {(void*)s->d_box, (void*)s->d_node, (void*)s->d_order, (void*)s->d_bsum, (void*)s->d_boff, (void*)s->d_err})
+  for (void* p : {(void*)s->d_box, (void*)s->d_node, (void*)s->d_order, (void*)s->d_bsum, (void*)s->d_boff, (void*)s->d_err, (void*)s->d_nline})
     if (p) (void)hipFree(p);
   delete s;
 }
